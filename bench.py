@@ -85,6 +85,9 @@ def parse():
                     help="rank 0 draws the GLOBAL batch and scatters it over RCCL (the round-1..5 input path: 2.2 GB at 8 x 576 clips); default: every "
                          "rank draws its own shard from (seed, rank).  The time either takes is reported (inputs.ms), outside the timed region")
     ap.add_argument("--no-pin", action="store_true", help="do not pin the ranks of a multi-rank job to their GPU's NUMA cores (dp.pin_rank_to_gpu_numa)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0: the gathered token ids and sum log-probs "
+                         "of every utterance, and a fixed sample of its own audio features) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--stub-engine", action="store_true",
                     help="tests/test_dp_gloo.py: the whole control flow of main() -- barriers, input shards, timed steps, gather, per-rank times, the one "
                          "JSON line -- on CPU over gloo with stand-in engines (no GPU, no HIP library); never a measurement")
@@ -429,6 +432,36 @@ def in_situ_probe(dec, lib, xa, B: int, n_micro: int, algo_bytes: int, steps: in
                             f"({int(sum(len(d) for d in durs))} launches over {steps} extra untimed decode steps)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs writes at most this much in all
+DUMP_FEATURE_SAMPLE = 1 << 20        # audio-feature values kept when the tensor is larger (seeded positions, the same for every run)
+
+
+def dump_outputs(out_dir: str, tokens: torch.Tensor, sum_logprobs: torch.Tensor, audio_features: torch.Tensor) -> dict:
+    """`--dump-outputs DIR`: what the last timed step computed, as a caller of the path receives it, so that two builds of the project
+    can be compared output for output (the inputs are seeded: the same arguments give the same mel and the same weights).
+      tokens.npy                  [n_total, width] float64 (token ids, exact): every utterance's row as gathered on rank 0
+      sum_logprobs.npy            [n_total] float32: the sum of the sampled tokens' log-probabilities, per utterance
+      audio_features_sample.npy   float32: rank 0's encoder output, all of it when small, else DUMP_FEATURE_SAMPLE values at seeded
+      audio_features_index.npy    float64: the flat positions of those values (sorted)"""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = audio_features.reshape(-1)
+    if flat.numel() > DUMP_FEATURE_SAMPLE:
+        idx = np.unique(np.random.Generator(np.random.PCG64(2024)).integers(0, flat.numel(), DUMP_FEATURE_SAMPLE))
+        feats = flat[torch.as_tensor(idx, device=flat.device)]
+    else:
+        idx = np.arange(flat.numel())
+        feats = flat
+    arrays = {"tokens": tokens.detach().cpu().to(torch.float64).numpy(),
+              "sum_logprobs": sum_logprobs.detach().float().cpu().numpy(),
+              "audio_features_sample": feats.detach().float().cpu().numpy(),
+              "audio_features_index": idx.astype(np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte budget"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {"dir": out_dir, "bytes": int(total), "arrays": {name: list(a.shape) for name, a in arrays.items()}}
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks as FRESH child processes (one per GPU) through
     torch.distributed.run and relay rank 0's JSON line.  Nothing in this process has touched the GPU yet
@@ -726,6 +759,8 @@ def main():
         g_tok, g_lp = out
         gathered = {"rows": int(g_tok.shape[0]), "width": int(g_tok.shape[1]),
                     "token_checksum": int(g_tok.to(torch.int64).sum().item() % (1 << 31)), "rows_expected": int(n_total)}
+    # (before the probes below: they run the decoder and the encoder again, on the buffers the last step's results live in)
+    dumped = dump_outputs(args.dump_outputs, *out, last["xa"]) if args.dump_outputs and rank == 0 and out is not None else None
 
     # ---- where a step's time goes (GPU events of the timed steps; the review's "make the line tell the truth about the schedule") ----
     def _mean(xs):
@@ -1047,6 +1082,7 @@ def main():
             "inputs": dict(inputs, ms_per_rank=[round(x, 1) for x in per_rank_input_ms]),
             "affinity": dict(affinity, cpus_per_rank=[int(x) for x in per_rank_cpus], first_cpu_per_rank=[int(x) for x in per_rank_first]),
             "gathered": gathered,
+            "dumped_outputs": dumped,
             "decode_chain": (None if native is None else {k: v for k, v in native.chain_status().items() if k != "footprint"}),
             # what sits in HBM while the job runs: engine weights (hipMalloc'ed by the library: weight-only encoder / cross-K/V
             # matrices are resident ONCE, as their fp16 expansion), everything torch allocated for the path (mel, encoder output,

@@ -225,6 +225,40 @@ def test_bench_main_control_flow_world2_gloo(tmp_path, extra):
         assert sf["tokens_match_the_limits"] is True and sf["useful_tokens_per_s"] > 0 and sf["ms_per_batch_pipelined"] is not None
 
 
+def test_bench_dump_outputs_are_the_last_steps_results_and_repeat(tmp_path):
+    """`bench.py --dump-outputs DIR` (one rank, stand-in engines): after the timed steps DIR holds the last step's gathered token rows and
+    sum log-probs and a sample of its audio features as float32 / float64 .npy files within 64 MB; a second run with the same arguments
+    writes the same arrays, and the line reports the requested number of timed steps and ms_per_step."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "3",
+               "--decode-steps", "5", "--stub-engine", "--length-dist", "forced", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300,
+                           env={k_: v for k_, v in os.environ.items() if k_ not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        arrays = {p.stem: np.load(p) for p in sorted(d.glob("*.npy"))}
+        assert set(arrays) == {"tokens", "sum_logprobs", "audio_features_sample", "audio_features_index"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20 and line["dumped_outputs"]["bytes"] == sum(a.nbytes for a in arrays.values())
+        assert arrays["tokens"].shape == (3, 3 + 5) and arrays["sum_logprobs"].shape == (3,)
+        runs.append(arrays)
+    g = torch.Generator().manual_seed(1234)              # the stand-in's rows are a function of the clip: the dumped rows are the last step's
+    mel = (torch.randn((3, 80, 3000), generator=g) * 0.5).clamp_(-0.5, 1.5).half()
+    sys.path.insert(0, root)
+    import bench
+    assert np.array_equal(runs[0]["tokens"], bench._StubEngines.token_rows(mel.float().mean(dim=(1, 2)), 8).double().numpy())
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
+
+
 def test_rank_placement_plan():
     """dp.plan_rank_cpus: ranks that share their GPU's NUMA node get disjoint slices of it; an unknown node falls back to even slices."""
     node_cpus = {0: list(range(0, 48)) + list(range(96, 144)), 1: list(range(48, 96)) + list(range(144, 192))}
