@@ -19,19 +19,24 @@ cross K/V ("the configuration the metric is quoted on"); random-init weights (no
 on any box), KV scales calibrated with the reference's rule (torch_whisper_convert.py -kv).
 
 Prints ONE JSON line (rank 0): value = decoded tokens per second over the whole job
-(n_gpus * B * T tokens per step / step time), plus `rtf`, `roofline` for the dominant kernel (decode
-cross-attention, HBM-bound: measured in situ with HIP events on its launch stream) and
-`cpu_baseline` (the oracle, a port of the reference's PyTorch path, timed on this box's host cores: one full-depth clip).
+(n_gpus * B * T tokens per step / step time), plus `rtf` and where a timed step's time goes (`pipeline`).
+A plain run does only what that line needs: it builds the engines, warms up, times the steps, writes
+--dump-outputs and prints.  --full adds everything else, each after the timed steps: `roofline` for the
+dominant kernel (decode cross-attention, HBM-bound: measured in situ with HIP events on its launch stream),
+the encoder alone, the second figure (--length-dist), `wer` and `cpu_baseline` (the oracle, a port of the
+reference's PyTorch path, timed on this box's host cores: one full-depth clip).
 `python bench.py --gpus N` without a launcher starts the N ranks itself (fresh child processes).
 """
 from __future__ import annotations
 
 import argparse
+import atexit
 import ctypes as C
 import json
 import os
 import shutil
 import sys
+import tempfile
 import time
 from pathlib import Path
 
@@ -67,18 +72,23 @@ def parse():
     ap.add_argument("--model", type=str, default="large-v2")
     ap.add_argument("--config", type=str, default="int8", choices=list(CONFIGS))
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--engine-cache", type=str, default="/tmp/wm_bench_engines")
+    ap.add_argument("--engine-cache", type=str, default=None, metavar="DIR",
+                    help="build the engines into DIR and reuse them from there in later runs (lab A/Bs on one box); default: a directory "
+                         "of this run's own, removed when the run ends, so that no run reads what an earlier one built")
     ap.add_argument("--encoder-cus", type=int, default=96,
                     help="CUs the next step's encoder runs on beside the current step's decode loop (0: no pipelining, one stage after the other)")
     ap.add_argument("--groups", type=int, default=0, help="utterance groups of the decode loop (0: the library's choice)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: the roofline probes, the second figure, "
+                         "the wer block and the cpu_baseline leg (each can be left out with the options below)")
     ap.add_argument("--length-dist", type=str, default="librispeech-like", choices=["forced", "librispeech-like"],
-                    help="SECOND figure beside the headline (which always decodes --decode-steps forced tokens per utterance): "
+                    help="--full: SECOND figure beside the headline (which always decodes --decode-steps forced tokens per utterance): "
                          "extra untimed-for-the-headline steps in which utterances end after LibriSpeech-like token counts "
                          "(per-row completion: finished rows drop out of the attention kernels); forced = skip it")
     ap.add_argument("--no-measure-traffic", action="store_true",
-                    help="do not run the rocprofv3 --pmc FETCH_SIZE pass of the dominant kernel (roofline.traffic then comes from the committed pass)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="--full: do not run the rocprofv3 --pmc FETCH_SIZE pass of the dominant kernel (roofline.traffic then comes from the committed pass)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no cpu_baseline leg and no wer block")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: no roofline probes")
     ap.add_argument("--eager-loop", action="store_true", help="lab: the decode loop with eager launches instead of replayed graphs (A/B runs of launch-level experiments)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even with one rank (self-test)")
     ap.add_argument("--scatter-inputs", action="store_true",
@@ -619,6 +629,9 @@ def main():
     rt = _StubRuntime() if args.stub_engine else _GpuRuntime()
     if args.stub_engine:            # the control-flow test: nothing below may touch a GPU, the probes are off
         args.no_roofline = args.no_cpu_baseline = args.no_measure_traffic = True
+    if not args.full:               # a plain run: the timed steps and the line, nothing measured beside them
+        args.no_roofline = args.no_cpu_baseline = args.no_measure_traffic = True
+        args.length_dist = "forced"
     # host placement BEFORE the first GPU call (the runtime's and torch's threads inherit the mask): every rank of a multi-rank job on the
     # CPUs next to its GPU, ranks that share a NUMA node on disjoint slices of it.  One rank alone is left where the OS put it (nothing to
     # keep apart -- and the cpu_baseline leg of a one-rank run wants every core)
@@ -644,8 +657,18 @@ def main():
         from encoding import WhisperEncoding
         lib = native.load_library()
 
-    # ---- engines: rank 0 builds once per box, everybody loads its own replica ----------------------
-    eng_dir = Path(args.engine_cache) / f"{args.model}-{args.config}-seed{args.seed}"
+    # ---- engines: rank 0 builds them, everybody loads its own replica.  By default into a directory of this run's own (its name
+    # travels from rank 0 to the others), removed when the run ends; --engine-cache DIR keeps them there for later runs ----------
+    cache = args.engine_cache
+    if cache is None and not args.stub_engine:
+        if rank == 0:
+            cache = tempfile.mkdtemp(prefix="wm_bench_engines_")
+            atexit.register(shutil.rmtree, cache, True)
+        if use_dist:
+            box = [cache]
+            dist.broadcast_object_list(box, src=0)
+            cache = box[0]
+    eng_dir = Path(cache or ".") / f"{args.model}-{args.config}-seed{args.seed}"
     build_s = 0.0
     if rank == 0 and not args.stub_engine and not (eng_dir / "decoder_config.json").exists():
         eng_dir.parent.mkdir(parents=True, exist_ok=True)

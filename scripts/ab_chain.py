@@ -9,7 +9,7 @@ import sys, os
 sys.path[:0] = [%r, %r]
 import native
 native.load_library().wm_set_decode_chain(int(sys.argv[1]))
-sys.argv = ["bench.py", "--batch", sys.argv[2], "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--length-dist", "forced", "--no-measure-traffic"]
+sys.argv = ["bench.py", "--batch", sys.argv[2], "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--length-dist", "forced", "--no-measure-traffic"]
 import bench
 bench.main()
 """ % (ROOT, os.path.join(ROOT, "eddie-wang-hackathon2023_amd"))

@@ -1,7 +1,7 @@
 """Round 4: temperature / best_of through the fused device loop.  best_of = 5 candidates of 64 utterances (320 rows, the draw inside
 the greedy kernel) against the greedy loop over 320 utterances (the same rows, arg-max), and against the literal host loop the
-options used to take (main_loop_reference: one decode() per token, host filters, torch's Categorical).  Engines: the ones bench.py
-caches (large-v2, weight-only int8 + int8 KV).      python scripts/bench_sampling.py [tokens=32]"""
+options used to take (main_loop_reference: one decode() per token, host filters, torch's Categorical).  Engines: the ones
+`bench.py --engine-cache /tmp/wm_bench_engines` keeps (large-v2, weight-only int8 + int8 KV).      python scripts/bench_sampling.py [tokens=32]"""
 import os, sys, time
 from pathlib import Path
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +13,7 @@ from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 eng = Path("/tmp/wm_bench_engines/large-v2-int8-seed0")
-assert (eng / "decoder_config.json").exists(), "run bench.py once first: it builds and caches the engines"
+assert (eng / "decoder_config.json").exists(), "run bench.py --engine-cache /tmp/wm_bench_engines once first: it builds the engines and keeps them there"
 dims = synthetic.DIMS["large-v2"]
 enc = WhisperEncoding(eng)
 g = torch.Generator(device="cuda").manual_seed(1234)

@@ -110,7 +110,7 @@ def read():
     model = "large-v2"
     n_rows = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     dims = SimpleNamespace(**synthetic.DIMS[model])
-    sys.argv = ["bench.py", "--model", model]
+    sys.argv = ["bench.py", "--model", model, "--engine-cache", "/tmp/wm_bench_engines"]
     args = bench.parse()
     eng_dir = Path(args.engine_cache) / f"{args.model}-{args.config}-seed{args.seed}"
     if not (eng_dir / "decoder_config.json").exists():

@@ -8,6 +8,6 @@ for b in ${BATCHES:-4 8}; do
   t=$(find $d -name "*kernel_trace.csv" | head -1)
   python scripts/step_timeline.py $t > gpurun_out/${tag}_step_timeline_b$b.txt
   rm -f $t
-  python bench.py --batch $b --steps 5 --warmup 1 --no-cpu-baseline --no-measure-traffic --length-dist forced 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().split('\n')[-1]); print('unprofiled: batch', $b, d['roofline']['decode_step_ms'], 'ms per token')" >> gpurun_out/${tag}_step_timeline_b$b.txt
+  python bench.py --batch $b --steps 5 --warmup 1 --full --no-cpu-baseline --no-measure-traffic --length-dist forced 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().split('\n')[-1]); print('unprofiled: batch', $b, d['roofline']['decode_step_ms'], 'ms per token')" >> $(dirname $d)/${tag}_step_timeline_b$b.txt
   cat gpurun_out/${tag}_step_timeline_b$b.txt
 done

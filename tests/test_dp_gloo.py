@@ -177,12 +177,13 @@ def _bench_main_worker(rank, world, port, out_dir, extra):
     assert not dist.is_initialized()          # main() tore its process group down (before rank 0's host-side epilogue)
 
 
-@pytest.mark.parametrize("extra", [(), ("--scatter-inputs",), ("--encoder-cus", "0", "--length-dist", "forced")])
+@pytest.mark.parametrize("extra", [(), ("--scatter-inputs",), ("--encoder-cus", "0", "--length-dist", "forced"), ("--full",),
+                                   ("--full", "--scatter-inputs")])
 def test_bench_main_control_flow_world2_gloo(tmp_path, extra):
     """the WHOLE control flow of bench.main with two ranks before an 8-GPU node ever runs it -- placement of the ranks,
     per-rank input shards (or the scatter from rank 0), warm-up, the barrier-bracketed timed steps with the pipelined encoder hand-over,
-    the gather of every step, max-over-ranks, the per-rank lists, the second figure's extra batches, the final barrier and the
-    process group's teardown BEFORE rank 0's host-side epilogue -- on CPU over gloo with stand-in engines (bench.py --stub-engine).
+    the gather of every step, max-over-ranks, the per-rank lists, the second figure's extra batches (--full only), the final barrier and
+    the process group's teardown BEFORE rank 0's host-side epilogue -- on CPU over gloo with stand-in engines (bench.py --stub-engine).
     Exactly ONE JSON line, from rank 0, with n_gpus 2; the gathered rows are both ranks' rows in utterance order."""
     import json
     port = _free_port()
@@ -220,9 +221,11 @@ def test_bench_main_control_flow_world2_gloo(tmp_path, extra):
     n_before = len(aff[0][1].split(","))
     if n_before >= 2:
         assert d["affinity"]["pinned"] and sets[0].isdisjoint(sets[1]) and sum(d["affinity"]["cpus_per_rank"]) <= n_before
-    if "--length-dist" not in extra:
+    if "--full" in extra:
         sf = d["second_figure"]
         assert sf["tokens_match_the_limits"] is True and sf["useful_tokens_per_s"] > 0 and sf["ms_per_batch_pipelined"] is not None
+    else:                                       # a plain run measures nothing beside its timed steps
+        assert d["second_figure"] is None and d["roofline"] is None
 
 
 def test_bench_dump_outputs_are_the_last_steps_results_and_repeat(tmp_path):

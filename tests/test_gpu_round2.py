@@ -204,12 +204,12 @@ def test_decoder_state_is_one_buffer_set(tmpdir_module):
 
 # ---------------------------------------------------------------------------------------------- bench.py through RCCL, one rank
 def test_bench_force_dist_single_rank(tmp_path):
-    """`bench.py --gpus 1 --force-dist`: torch.distributed over RCCL initialised, mel scatter and token gather run
-    as collectives on one rank, the printed line carries n_gpus == --gpus.  (N > 1 is the driver's to launch: `bench.py
+    """`bench.py --gpus 1 --force-dist --full`: torch.distributed over RCCL initialised, mel scatter and token gather run
+    as collectives on one rank, the printed line carries n_gpus == --gpus and the roofline.  (N > 1 is the driver's to launch: `bench.py
     --gpus N` starts its N ranks itself, tests/test_dp_gloo.py covers the launcher and the N = 2 data path on gloo.)"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--model", "tiny", "--config", "int8",
-           "--batch", "16", "--decode-steps", "8", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+           "--batch", "16", "--decode-steps", "8", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--engine-cache", str(tmp_path / "engines")]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
