@@ -21,54 +21,9 @@
 // bookkeeping are what the tests hold to the reference.
 #include "common.h"
 #include "kernels.h"
+#include "logit_rules.h"
 
 namespace wm {
-
-struct MS { float m, s; };                       // running max and sum of exp(x - m)
-__device__ __forceinline__ MS ms_add(MS a, float x) {
-    if (x == -INFINITY) return a;
-    if (x > a.m) { a.s = a.s * __expf(a.m - x) + 1.f; a.m = x; }
-    else a.s += __expf(x - a.m);
-    return a;
-}
-__device__ __forceinline__ MS ms_merge(MS a, MS b) {
-    if (b.m == -INFINITY) return a;
-    if (a.m == -INFINITY) return b;
-    const float m = fmaxf(a.m, b.m);
-    return MS{m, a.s * __expf(a.m - m) + b.s * __expf(b.m - m)};
-}
-struct AM { float v; int i; };                   // arg-max with first-index tie break
-__device__ __forceinline__ AM am_merge(AM a, AM b) {
-    if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-    return a;
-}
-
-template <typename T, typename F>
-__device__ __forceinline__ T wave_reduce(T v, F merge) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        T other;
-        // shuffle the struct field-wise (two 32-bit words)
-        static_assert(sizeof(T) == 8, "pair types only");
-        unsigned long long bits = __builtin_bit_cast(unsigned long long, v);
-        unsigned lo = __shfl_xor((unsigned)bits, o), hi = __shfl_xor((unsigned)(bits >> 32), o);
-        other = __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
-        v = merge(v, other);
-    }
-    return v;
-}
-template <typename T, typename F>
-__device__ __forceinline__ T block_reduce(T v, F merge, T* scratch) {
-    v = wave_reduce(v, merge);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) scratch[wid] = v;
-    __syncthreads();
-    T r = scratch[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = merge(r, scratch[w]);
-    __syncthreads();
-    return r;
-}
 
 constexpr int GREEDY_THREADS = 1024;
 
@@ -91,56 +46,10 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_kernel(GreedyParams p) 
     const int cur_len = p.t_dev ? *p.t_dev + 1 : p.cur_len;     // device step counter holds n_past = cur_len - 1
     h16* lg = p.logits + (size_t)b * p.ld_row;
     int32_t* toks = p.tokens + (size_t)b * p.ld_tok;
-    const int tb = p.timestamp_begin;
-    // apply_rules: 0 plain arg-max; 1 SuppressBlank + SuppressTokens + ApplyTimestampRules (the default decoding options);
-    // 2 the two suppress filters WITHOUT the timestamp rules -- DecodingOptions.without_timestamps, where the reference builds no
-    // ApplyTimestampRules filter (W/decoding.py:337-346) and samples from the whole (suppressed) vocabulary
-    const bool lists = p.apply_rules != 0, ts_rules = p.apply_rules == 1;
-    const bool first = lists && (cur_len == p.sample_begin);
-
-    // ---- SuppressTokens (+ no_timestamps) and SuppressBlank: written into the logits row, exactly
-    // like the reference's in-place filters (decoding.py:202-217); the scan below then sees -inf ----
-    if (lists) {
-        const h16 ninf = (h16)(-INFINITY);
-        for (int i = tid; i < p.n_suppress; i += GREEDY_THREADS) lg[p.suppress[i]] = ninf;
-        if (first) for (int i = tid; i < p.n_blank; i += GREEDY_THREADS) lg[p.blank[i]] = ninf;
-    }
-    // ---- token-history facts: last / penultimate sampled token, last timestamp.  Every thread looks at one sampled token
-    // (a backwards scan by one thread was a chain of dependent loads: up to one L2 round trip per sampled token) ------------
-    const int n_sampled = cur_len - p.sample_begin;
-    int my_rel = -1, my_tok = -1;                  // this thread's latest timestamp among the sampled tokens it looked at
-    if (ts_rules) {
-        for (int j = tid; j < n_sampled; j += GREEDY_THREADS) {
-            const int t = toks[p.sample_begin + j];
-            if (t >= tb) { my_rel = j; my_tok = t; }
-            if (j == n_sampled - 1) s_info[0] = t >= tb;
-            if (j == n_sampled - 2) s_info[1] = t >= tb;
-        }
-    }
-    {
-        int r = my_rel;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) r = max(r, __shfl_xor(r, o));
-        if ((tid & 63) == 0) s_hist[tid >> 6] = r;
-    }
-    __syncthreads();                       // also orders the -inf stores above before the scan
-    int rel_last = -1;
-#pragma unroll
-    for (int w = 0; w < GREEDY_THREADS / 64; ++w) rel_last = max(rel_last, s_hist[w]);
-    if (rel_last >= 0 && my_rel == rel_last) s_info[2] = my_tok;          // exactly one thread holds that position
-    __syncthreads();
-    const bool last_ts = ts_rules && n_sampled >= 1 && s_info[0];
-    const bool pen_ts = ts_rules && (n_sampled < 2 || s_info[1]);
-    int ts_last = rel_last >= 0 ? s_info[2] : -1;
-    if (ts_last >= 0 && !(last_ts && !pen_ts)) ts_last += 1;
-
-    // allowed = [lo_txt, hi_txt) U [lo_ts, hi_ts): every rule of ApplyTimestampRules is a range
-    int lo_txt = 0, hi_txt = ts_rules ? tb : p.V, lo_ts = ts_rules ? tb : p.V, hi_ts = p.V;
-    if (ts_rules) {
-        if (first) { hi_txt = 0; if (p.max_initial_ts >= 0) hi_ts = min(hi_ts, tb + p.max_initial_ts + 1); }
-        if (last_ts) { if (pen_ts) lo_ts = p.V; else lo_txt = max(lo_txt, p.eot); }
-        if (ts_last >= 0) lo_ts = max(lo_ts, ts_last);
-    }
+    // suppress lists, token-history facts and the allowed ranges [lo_txt, hi_txt) U [lo_ts, hi_ts): logit_rules.h
+    const RowRules rr = row_rules<GREEDY_THREADS>(p, lg, toks, cur_len, s_info, s_hist);
+    const bool ts_rules = rr.ts_rules;
+    const int lo_txt = rr.lo_txt, hi_txt = rr.hi_txt, lo_ts = rr.lo_ts, hi_ts = rr.hi_ts;
 
     MS txt{-INFINITY, 0.f}, tsm{-INFINITY, 0.f};
     AM atxt{-INFINITY, 0x7fffffff}, ats{-INFINITY, 0x7fffffff};

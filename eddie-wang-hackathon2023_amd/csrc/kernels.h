@@ -235,6 +235,24 @@ int launch_step_advance(int32_t* counter, hipStream_t stream);
 int launch_step_finish(int32_t* counter, const int32_t* done, int B, int32_t* live, hipStream_t stream);
 int launch_argmax(const h16* logits, long ld_row, int B, int V, int32_t* ids, hipStream_t stream);
 
+// ---------------------------------------------------------------- beam.hip
+constexpr int BEAM_MAX = 8, BEAM_POOL_MAX = 16;
+struct BeamCand { float lp; int32_t tok; };  // one proposal of a row: log-probability and token (-1: none)
+struct BeamParams {
+    GreedyParams g;                          // logits, tokens, sums, rule lists, done / n_done / row_limit / t_dev; B = rows
+    int K, max_cand, ignore_eot;             // beam size, pool size
+    int32_t* parent;                         // [rows]
+    int32_t* fin_tokens; float* fin_scores; int32_t* fin_len; int32_t* fin_count;    // pool, per utterance
+    int32_t* live_len;                       // [n_audio]
+    BeamCand* cand;                          // [rows][K + 1] scratch between the two launches
+};
+int launch_beam_step(const BeamParams& p, hipStream_t stream);
+struct KvReorderParams {
+    void* const* layers; int n_layer, rows, K, H, cap, elem_bytes;
+    const int32_t* parent; const int32_t* done; int n_last; const int32_t* t_dev;
+};
+int launch_kv_reorder(const KvReorderParams& p, hipStream_t stream);
+
 // ---------------------------------------------------------------- frontend.hip
 size_t log_mel_workspace_bytes(int batch, int n_samples, int n_mels);
 int launch_log_mel(const float* audio, int batch, int n_samples, long audio_ld, const float* filters, int n_mels,

@@ -16,7 +16,10 @@ What differs underneath:
   `main_loop_reference` is the literal per-step loop through `decode()` and the host-side filter
   classes, kept for parity tests: both must return identical tokens;
 * the cross-attention K/V computed by `detect_language` are re-used by `main_loop` for the same
-  audio features (the reference runs that engine twice per utterance).
+  audio features (the reference runs that engine twice per utterance, SURVEY F6);
+* `beam_size` / `patience` select beam search (upstream Whisper's BeamSearchDecoder; the reference carries the options
+  but no such class): `BeamSearchDecoder` in the literal loops, wm_beam_step + wm_kv_reorder (csrc/beam.hip) after
+  every decoder launch of `main_loop`.
 """
 from __future__ import annotations
 
@@ -183,6 +186,136 @@ class GreedyDecoder:
         return F.pad(tokens, (0, 1), value=self.eot), sum_logprobs.tolist()
 
 
+BEAM_MAX, BEAM_POOL_MAX = 8, 16          # bounds of csrc/beam.hip
+
+
+def check_decoding_options(options: DecodingOptions) -> None:
+    """The combinations of sampling options the decoders take (upstream Whisper refuses the same ones)."""
+    if options.beam_size is not None:
+        if options.best_of is not None:
+            raise ValueError("beam_size and best_of can't be given together")
+        if options.temperature != 0:
+            raise ValueError("beam_size needs temperature = 0 (beam search does not sample)")
+        if not 1 <= options.beam_size <= BEAM_MAX:
+            raise ValueError(f"beam_size {options.beam_size} outside 1..{BEAM_MAX}")
+        n = round(options.beam_size * (options.patience or 1.0))
+        if not 1 <= n <= BEAM_POOL_MAX:
+            raise ValueError(f"beam_size * patience = {n} finished candidates per utterance, outside 1..{BEAM_POOL_MAX}")
+    elif options.patience is not None:
+        raise ValueError("patience requires beam_size to be given")
+
+
+class BeamSearchDecoder:
+    """Beam search with the semantics of upstream Whisper's BeamSearchDecoder, in torch on the host: the literal statement of
+    the contract that the device step (csrc/beam.hip, wm_beam_io in include/whisper_mi355.h) implements.
+
+    Rows are n_audio x beam_size, beam j of utterance a is row a * beam_size + j.  Per `update`, per utterance:
+    every live beam proposes its beam_size + 1 best tokens (at the first sampled step only beam 0: the beams are identical);
+    candidates are walked in the TOTAL order score descending, parent beam ascending, token ascending (within a beam: equal
+    log-probabilities, lower token first; tokens at -inf are never proposed) -- fp16 logits tie exactly often enough that the
+    order must be a rule; EOT candidates go to the step's finished list, others become the next live beams until beam_size
+    are saved; the finished ones join the utterance's pool while it holds fewer than max_candidates = round(beam_size *
+    patience).
+
+    One deliberate difference from upstream: an utterance whose pool is full is FROZEN -- its live beams, sums and pool no
+    longer change.  Upstream keeps stepping it until the whole batch is complete, which (with patience < 1) makes an
+    utterance's candidates depend on its neighbours in the batch; here a row's result never depends on the other rows."""
+
+    def __init__(self, beam_size: int, eot: int, sample_begin: int, patience: Optional[float] = None):
+        self.beam_size, self.eot, self.sample_begin = beam_size, eot, sample_begin
+        self.patience = patience or 1.0
+        self.max_candidates: int = round(beam_size * self.patience)
+        assert self.max_candidates > 0, f"Invalid beam size ({beam_size}) or patience ({patience})"
+        self.reset()
+
+    def reset(self, n_audio: int = 0):
+        self.pool: List[List[Tuple[List[int], float]]] = [[] for _ in range(n_audio)]     # per utterance: (tokens with EOT, score)
+        self.live_len: List[Optional[int]] = [None] * n_audio                             # length of a frozen utterance's live beams
+        self.source_indices = None
+
+    @property
+    def completed(self) -> List[bool]:
+        return [n is not None for n in self.live_len]
+
+    def propose(self, logprobs: np.ndarray) -> List[int]:
+        """The beam_size + 1 best tokens of one row: log-probability descending, token ascending among equals."""
+        k = min(self.beam_size + 1, logprobs.shape[0])
+        kth = np.partition(logprobs, -k)[-k]                       # everything >= the k-th largest value, ties included
+        idx = np.nonzero((logprobs >= kth) & (logprobs > -np.inf))[0]
+        idx = idx[np.lexsort((idx, -logprobs[idx]))]               # (last key first: value, then token id)
+        return [int(t) for t in idx[:k]]
+
+    def update(self, tokens: Tensor, logits: Tensor, sum_logprobs: Tensor) -> Tuple[Tensor, bool, Tensor]:
+        """One token step.  Returns (tokens with the new column, every utterance complete, source row of every row) and
+        overwrites `sum_logprobs`; the caller gathers its self-attention cache by the source rows."""
+        K, eot = self.beam_size, self.eot
+        n_rows, cur = tokens.shape
+        assert n_rows % K == 0, f"{n_rows} rows are not a multiple of beam_size {K}"
+        n_audio = n_rows // K
+        if len(self.pool) != n_audio:
+            self.reset(n_audio)
+        logprobs = F.log_softmax(logits.float(), dim=-1).cpu().numpy()
+        sums = sum_logprobs.detach().cpu().numpy().astype(np.float32)
+        old = tokens.cpu().tolist()
+        rows, new_sums, source = [], [], []
+        for a in range(n_audio):
+            r0 = a * K
+            if self.live_len[a] is not None:                      # frozen: rows keep their content (the new column is padding)
+                rows += [old[r0 + j] + [eot] for j in range(K)]
+                new_sums += [float(sums[r0 + j]) for j in range(K)]
+                source += [r0 + j for j in range(K)]
+                continue
+            cands = []                                            # (score, beam, token)
+            for j in range(1 if cur == self.sample_begin else K):
+                for t in self.propose(logprobs[r0 + j]):
+                    cands.append((np.float32(sums[r0 + j] + logprobs[r0 + j, t]), j, t))
+            cands.sort(key=lambda c: (-c[0], c[1], c[2]))
+            live, finished = [], []
+            for score, j, t in cands:
+                if t == eot:
+                    finished.append((old[r0 + j] + [eot], float(score)))
+                else:
+                    live.append((score, j, t))
+                    if len(live) == K:
+                        break
+            while len(live) < K:                                  # fewer finite proposals than beams (never under Whisper's rules)
+                live.append((np.float32(-np.inf), len(live), eot))
+            for score, j, t in live:
+                rows.append(old[r0 + j] + [t])
+                new_sums.append(float(score))
+                source.append(r0 + j)
+            for seq in finished:
+                if len(self.pool[a]) >= self.max_candidates:
+                    break
+                self.pool[a].append(seq)
+            if len(self.pool[a]) >= self.max_candidates:
+                self.live_len[a] = cur + 1
+        sum_logprobs[:] = torch.tensor(new_sums, dtype=sum_logprobs.dtype, device=sum_logprobs.device)
+        self.source_indices = torch.tensor(source, dtype=torch.long, device=tokens.device)
+        tokens = torch.tensor(rows, dtype=tokens.dtype, device=tokens.device)
+        return tokens, all(self.completed), self.source_indices
+
+    def finalize(self, tokens: Tensor, sum_logprobs: Tensor):
+        """Per utterance: the pool, topped up with the live beams (best sum first, each closed with EOT) while it holds
+        fewer than beam_size sequences.  Lists per utterance, of differing lengths."""
+        K = self.beam_size
+        tokens = tokens.reshape(-1, K, tokens.shape[-1]).cpu()
+        sums = sum_logprobs.reshape(-1, K).cpu().tolist()
+        if len(self.pool) != tokens.shape[0]:
+            self.reset(tokens.shape[0])
+        out_tokens, out_sums = [], []
+        for a in range(tokens.shape[0]):
+            seqs = list(self.pool[a])
+            n_live = tokens.shape[-1] if self.live_len[a] is None else self.live_len[a]
+            for j in sorted(range(K), key=lambda j: (-sums[a][j], j)):
+                if len(seqs) >= K:
+                    break
+                seqs.append((tokens[a, j, :n_live].tolist() + [self.eot], sums[a][j]))
+            out_tokens.append([torch.tensor(s, dtype=torch.long) for s, _ in seqs])
+            out_sums.append([lp for _, lp in seqs])
+        return out_tokens, out_sums
+
+
 class WhisperDecoding:
     def __init__(self, engine_dir, only_torch: bool = False, vocab_path: Optional[str] = None,
                  options: Optional[DecodingOptions] = None):
@@ -204,6 +337,7 @@ class WhisperDecoding:
         self.tokens = torch.tensor([self.initial_tokens]).repeat(self.decoder_config['num_audio'], 1)
         self.sot_index = self.initial_tokens.index(self.tokenizer.sot)
         self.options = options or DecodingOptions()
+        check_decoding_options(self.options)
 
         self.n_group = self.options.beam_size or self.options.best_of or 1
         self.sample_len: int = self.options.sample_len or self.decoder_config['num_text_ctx'] // 2
@@ -236,7 +370,11 @@ class WhisperDecoding:
             self.logit_filters.append(
                 ApplyTimestampRules(self.tokenizer, self.sample_begin, self.max_initial_timestamp_index))
         self.sequence_ranker = MaximumLikelihoodRanker(self.options.length_penalty)
-        self.decoder = GreedyDecoder(self.options.temperature, self.tokenizer.eot)
+        if self.options.beam_size is not None:
+            self.decoder = BeamSearchDecoder(self.options.beam_size, self.tokenizer.eot, self.sample_begin, self.options.patience)
+        else:
+            self.decoder = GreedyDecoder(self.options.temperature, self.tokenizer.eot)
+        self.beam = self.options.beam_size is not None     # (beam_size = 1 is beam search too: one beam, a pool of finished candidates)
 
         self.kv_cache = {}
         self.hooks = []
@@ -597,7 +735,8 @@ class WhisperDecoding:
         logits = logits[:, -1]
         for logit_filter in self.logit_filters:
             logit_filter.apply(logits, tokens)
-        return self.decoder.update(tokens, logits, sum_logprobs)
+        out = self.decoder.update(tokens, logits, sum_logprobs)
+        return out if len(out) == 3 else (*out, None)       # (tokens, completed, source rows of a beam step or None)
 
     def main_loop_reference(self, audio_features):
         """The reference's loop verbatim in structure (W/decoding.py:785-821): one `decode()` per token,
@@ -610,10 +749,14 @@ class WhisperDecoding:
         if self.n_group > 1:        # best_of / beam candidates share their utterance's audio (upstream Whisper repeats it too)
             audio_features = audio_features.repeat_interleave(self.n_group, dim=0)
         cross = self.xa2cross_key_value(audio_features)
+        if self.beam:
+            self.decoder.reset(audio_features.shape[0] // self.n_group)
         for i in range(self.sample_len):
             feed = tokens if tokens.shape[-1] <= self.initial_token_length else tokens[:, -1:]
             logits, past_key_value = self.decode(feed, cross, past_key_value)
-            tokens, completed = self._host_step(i, logits, tokens, sum_logprobs, no_speech_probs)
+            tokens, completed, source = self._host_step(i, logits, tokens, sum_logprobs, no_speech_probs)
+            if source is not None and past_key_value is not None:       # the caches follow their beams
+                past_key_value = [kv[source.to(kv.device)] for kv in past_key_value]
             if completed or tokens.shape[-1] > self.decoder_config['num_text_ctx']:
                 break
         return tokens, sum_logprobs, no_speech_probs
@@ -625,12 +768,19 @@ class WhisperDecoding:
             n_batch = tokens.shape[0]
             sum_logprobs: Tensor = torch.zeros(n_batch, device=audio_features.device)
             no_speech_probs = [np.nan] * n_batch
+            if self.beam:
+                self.decoder.reset(audio_features.shape[0])
+                audio_features = audio_features.repeat_interleave(self.n_group, dim=0)     # beams share their utterance's audio
             for i in range(self.sample_len):
                 if not self.kv_cache:
                     self.kv_cache, self.hooks = model.install_kv_cache_hooks()
                 feed = tokens if tokens.shape[-1] <= self.initial_token_length else tokens[:, -1:]
                 logits = model.decoder(feed, audio_features, kv_cache=self.kv_cache)
-                tokens, completed = self._host_step(i, logits, tokens, sum_logprobs, no_speech_probs)
+                tokens, completed, source = self._host_step(i, logits, tokens, sum_logprobs, no_speech_probs)
+                if source is not None:                                   # the cached keys / values follow their beams (every per-row entry, as upstream)
+                    for key, value in list(self.kv_cache.items()):
+                        if torch.is_tensor(value) and value.shape[0] == source.shape[0]:
+                            self.kv_cache[key] = value[source]
                 if completed or tokens.shape[-1] > self.decoder_config['num_text_ctx']:
                     break
         for hook in self.hooks:
@@ -691,6 +841,21 @@ class WhisperDecoding:
             suppress=torch.tensor(suppress or [0], dtype=torch.int32, device=device), n_suppress=len(suppress),
             blank=torch.tensor(blank or [0], dtype=torch.int32, device=device), n_blank=len(blank),
         )
+        if self.beam:
+            # the beam step's outputs: parents, the pool of finished candidates per utterance, the proposals between its two launches
+            K, MC = self.decoder.beam_size, self.decoder.max_candidates
+            n_audio = n_batch // K
+            st.update(
+                parent=torch.zeros(n_batch, dtype=torch.int32, device=device),
+                fin_tokens=torch.zeros((n_audio, MC, cap + 1), dtype=torch.int32, device=device),
+                fin_scores=torch.zeros((n_audio, MC), dtype=torch.float32, device=device),
+                fin_len=torch.zeros((n_audio, MC), dtype=torch.int32, device=device),
+                fin_count=torch.zeros(n_audio, dtype=torch.int32, device=device),
+                live_len=torch.zeros(n_audio, dtype=torch.int32, device=device),
+                beam_ws=torch.empty(max(1, native.load_library().wm_beam_workspace_bytes(n_batch, K)) if device.type == 'cuda' else 1,
+                                    dtype=torch.uint8, device=device),
+                kv_tables={},
+            )
         self._state[n_batch] = st
         return st
 
@@ -702,7 +867,11 @@ class WhisperDecoding:
         n_layer, n_head, cap, V = cfg['num_layers'], cfg['num_heads'], cfg['num_text_ctx'], cfg['vocab_size']
         kv = 2 * n_head * cap * 64 * (1 if self.use_int8_kv_cache else 2)
         cross = 2 * n_head * cfg['num_audio_ctx'] * 64 * (1 if self.use_int8_cross_kv else 2)
-        return n_layer * (kv + cross) + (cap + 1) * 4 + self.initial_token_length * V * 2 + 64
+        per_row = n_layer * (kv + cross) + (cap + 1) * 4 + self.initial_token_length * V * 2 + 64
+        if self.beam:       # parent + proposals per row, and the row's share of its utterance's pool (tokens, score, length) and counters
+            K, MC = self.decoder.beam_size, self.decoder.max_candidates
+            per_row += 4 + (K + 1) * 8 + -(-(MC * ((cap + 1) * 4 + 8) + 8) // K)
+        return per_row
 
     def _group_streams(self, n, dev):
         """Side streams of the utterance groups (never the legacy default stream: graphs are captured on them).
@@ -749,14 +918,20 @@ class WhisperDecoding:
             n_micro = 3 if n_batch >= 128 else 2 if n_batch >= 13 else 1
         else:
             n_micro = self.micro_batches if n_batch >= 4 * self.micro_batches else 1
-        return n_micro, [(g * n_batch // n_micro, (g + 1) * n_batch // n_micro) for g in range(n_micro)]
+        # the beams of an utterance stay in one group (the beam step and the cache reorder work per utterance): cut in whole utterances
+        unit = self.n_group if self.beam else 1
+        n_units = n_batch // unit
+        n_micro = max(1, min(n_micro, n_units))
+        return n_micro, [(g * n_units // n_micro * unit, (g + 1) * n_units // n_micro * unit) for g in range(n_micro)]
 
     def balanced_order(self, n_batch: int) -> List[int]:
         """For a batch whose rows are sorted by expected decode length: the permutation that deals them over the
         utterance groups (contiguous slices of the batch, `_groups`) like cards, so that every group holds short and long
         rows alike.  All groups then shrink together as rows finish -- their K/V streams and chains keep overlapping --
         instead of the group of the longest clips running on alone.  `batch[i] = sorted_batch[order[i]]`."""
-        n_micro, bounds = self._groups(n_batch)
+        unit = self.n_group if self.beam else 1        # (beam search: the groups are cut over the clips' beam rows, in whole clips)
+        n_micro, bounds = self._groups(n_batch * unit)
+        bounds = [(lo // unit, hi // unit) for lo, hi in bounds]
         room = [hi - lo for lo, hi in bounds]
         members = [[] for _ in bounds]
         g = 0
@@ -854,6 +1029,37 @@ class WhisperDecoding:
         io.temperature, io.row0, io.seed_dev = float(self.options.temperature), lo, st['seed'].data_ptr()
         native.check(native.load_library().wm_greedy_step(C.byref(io), stream), "wm_greedy_step")
 
+    def _beam(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, kv_table, ignore_eot, n_past_dev=None):
+        """Beam step + cache reorder for rows [lo, hi) (whole utterances) of the batch state `st`: wm_beam_step applies the logit rules,
+        picks and moves the beams, wm_kv_reorder lets every layer's self-attention cache rows follow their parents."""
+        tk, cfg, lib = self.tokenizer, self.decoder_config, native.load_library()
+        K, MC = self.decoder.beam_size, self.decoder.max_candidates
+        a_lo, a_hi = lo // K, hi // K
+        io = native.WmBeamIO()
+        io.logits, io.row_stride = logits_ptr, row_stride
+        io.batch, io.n_vocab = hi - lo, cfg['vocab_size']
+        io.tokens, io.tokens_ld, io.cur_len = st['tokens'][lo:hi].data_ptr(), st['tokens'].shape[1], cur_len
+        io.sum_logprobs = st['sum_logprobs'][lo:hi].data_ptr()
+        io.suppress, io.n_suppress = st['suppress'].data_ptr(), st['n_suppress']
+        io.blank, io.n_blank = st['blank'].data_ptr(), st['n_blank']
+        io.sample_begin, io.eot, io.timestamp_begin = self.sample_begin, tk.eot, tk.timestamp_begin
+        io.max_initial_timestamp_index = -1 if self.max_initial_timestamp_index is None else self.max_initial_timestamp_index
+        io.apply_rules = 2 if self.options.without_timestamps else 1
+        io.beam_size, io.max_candidates, io.ignore_eot = K, MC, int(bool(ignore_eot))
+        io.n_past_dev = n_past_dev.data_ptr() if n_past_dev is not None else None
+        io.row_limit = st['row_limit'][lo:hi].data_ptr()
+        io.parent = st['parent'][lo:hi].data_ptr()
+        io.fin_tokens, io.fin_scores = st['fin_tokens'][a_lo:a_hi].data_ptr(), st['fin_scores'][a_lo:a_hi].data_ptr()
+        io.fin_len, io.fin_count = st['fin_len'][a_lo:a_hi].data_ptr(), st['fin_count'][a_lo:a_hi].data_ptr()
+        io.live_len = st['live_len'][a_lo:a_hi].data_ptr()
+        io.done, io.n_done = st['done'][lo:hi].data_ptr(), st['n_done'].data_ptr()
+        ws = st['beam_ws'][lo * (K + 1) * 8: hi * (K + 1) * 8]
+        io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
+        native.check(lib.wm_beam_step(C.byref(io), stream), "wm_beam_step")
+        native.check(lib.wm_kv_reorder(kv_table.data_ptr(), cfg['num_layers'], hi - lo, K, cfg['num_heads'], cfg['num_text_ctx'],
+                                       1 if self.use_int8_kv_cache else 2, st['parent'][lo:hi].data_ptr(), st['done'][lo:hi].data_ptr(),
+                                       cur_len - 1, io.n_past_dev, stream), "wm_kv_reorder")
+
     def main_loop(self, audio_features, ignore_eot: bool = False, row_limit=None, _retry: bool = False):
         """Greedy decoding, fast path.  Same return values as the reference's main_loop
         (tokens int64 [n, <=n_text_ctx+1], sum_logprobs fp32 [n], no_speech_probs list).
@@ -867,7 +1073,7 @@ class WhisperDecoding:
         Rows that have emitted EOT drop out of the attention kernels and a group whose rows are all
         finished is no longer stepped (`skip_finished_rows`): the loop's cost follows the live rows."""
         features_in = audio_features
-        if self.options.temperature != 0 or self.n_group != 1:
+        if self.options.temperature != 0 or self.n_group != 1 or self.beam:
             # Sampling options (W/decoding.py:274-300 temperature, :92-115 best_of + ranker).  Round 4: the device loop takes them --
             # the draw is a Gumbel-max inside the greedy kernel, candidates are rows like any others.  `device_sampling = False`
             # (or tensors that are not on the GPU) keeps the literal host loop: torch's generator, the draws the goldens hold.
@@ -895,6 +1101,9 @@ class WhisperDecoding:
         st['sum_logprobs'].zero_()
         st['n_done'].zero_()
         st['done'].zero_()
+        if self.beam:
+            st['fin_count'].zero_()
+            st['live_len'].zero_()
         if row_limit is not None:
             row_limit = torch.as_tensor(row_limit).to(device=dev, dtype=torch.int32)
             assert row_limit.shape == (n_batch,)
@@ -902,6 +1111,8 @@ class WhisperDecoding:
         else:
             st['row_limit'].fill_(1 << 30)
         n_micro, bounds = self._groups(n_batch)
+        if self.cu_partition and n_micro > 1 and self.beam:
+            raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
         if self.cu_partition and n_micro > 1 and self.decoder_session.qkv_amax is None and row_limit is None:
             return self._main_loop_partitioned(audio_features, st, cross, L0, n_micro, bounds, ignore_eot)
         use_live = bool(self.skip_finished_rows) and not ignore_eot and max(hi - lo for lo, hi in bounds) <= 1024
@@ -914,6 +1125,10 @@ class WhisperDecoding:
                                kv=[t[lo:hi] for t in st['kv']], cross=[t[lo:hi] for t in cross],
                                logits=st['logits'][lo:hi], tokens=st['tokens'][lo:hi], done=st['done'][lo:hi],
                                live=self._live_list(st, n_micro, g, lo, hi) if use_live else None))
+            if self.beam:       # the group's cache rows per layer as a device-resident pointer table (wm_kv_reorder; stable like the buffers)
+                if (n_micro, g) not in st['kv_tables']:
+                    st['kv_tables'][(n_micro, g)] = torch.tensor([t.data_ptr() for t in groups[-1]['kv']], dtype=torch.int64, device=dev)
+                groups[-1]['kv_table'] = st['kv_tables'][(n_micro, g)]
         for s_ in streams:
             s_.wait_stream(main)
         cur = L0
@@ -933,6 +1148,14 @@ class WhisperDecoding:
             elif counter is not None:
                 native.check(lib.wm_step_advance(counter.data_ptr(), gr['stream']), "wm_step_advance")
 
+        def token_step(gr, logits_ptr, row_stride, cur_len, sm, n_past_dev=None):
+            # what follows a group's decoder launch: the fused greedy step, or the beam step and the cache reorder
+            if self.beam:
+                self._beam(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, gr['kv_table'], ignore_eot, n_past_dev=n_past_dev)
+            else:
+                self._greedy(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, n_past_dev=n_past_dev)
+
+        bkey = ('beam', bool(ignore_eot)) if self.beam else ()         # (ignore_eot is an argument of the captured beam step)
         last_issued = None
         for i in range(self.sample_len):
             for gr in groups:
@@ -943,18 +1166,18 @@ class WhisperDecoding:
                     if last_issued is not None:
                         streams[slot].wait_stream(streams[last_issued])
                     last_issued = slot
-                gkey = (n_micro, slot, use_live)
+                gkey = (n_micro, slot, use_live) + bkey
                 if i == 0:
                     # the prefill (L0 tokens on an empty cache) + the first greedy step.  Round 6: replayed from a graph from the second
                     # batch on -- the call is the same for every batch (state buffers, L0 and the start position are fixed), and issued
                     # eagerly its ~ 390 launches per group are HOST-bound at small and middle batches (7 us each: 2.7 ms per group where the
                     # GPU needs 1.7 at one utterance; with the language pass 9.5 ms per batch of 2 x 8)
-                    pkey = (n_micro, slot, use_live, 'prefill', L0, shared)
+                    pkey = (n_micro, slot, use_live, 'prefill', L0, shared) + bkey
 
                     def issue_prefill(gr=gr, lo=lo, hi=hi, sm=sm, slot=slot):
                         sess.decoder_step(gr['tokens'][:, :L0], pos[0:L0], gr['cross'], None, cap, gr['kv'], cap,
                                           gr['logits'], 0, sm, slot=slot, live_rows=gr['live'], not_alone=shared)
-                        self._greedy(st, lo, hi, gr['logits'].data_ptr() + (L0 - 1) * V * 2, L0 * V, L0, sm)
+                        token_step(gr, gr['logits'].data_ptr() + (L0 - 1) * V * 2, L0 * V, L0, sm)
                         finish_step(gr, None)
                     if use_graph and self.graph_prefill and pkey in st['graphs']:
                         with torch.cuda.stream(streams[slot]):
@@ -974,7 +1197,7 @@ class WhisperDecoding:
                 else:
                     sess.decoder_step(gr['tokens'][:, cur - 1:cur], pos[cur - 1:cur], gr['cross'], gr['kv'], cap,
                                       gr['kv'], cap, gr['logits'], cur - 1, sm, slot=slot, live_rows=gr['live'], not_alone=shared)
-                    self._greedy(st, lo, hi, gr['logits'].data_ptr(), V, cur, sm)
+                    token_step(gr, gr['logits'].data_ptr(), V, cur, sm)
                     finish_step(gr, None)
                     if use_graph:
                         # capture ONE decode step (decoder + fused greedy + counter advance) of this group;
@@ -994,7 +1217,7 @@ class WhisperDecoding:
                             sess.decoder_step(gr['tokens'], pos, gr['cross'], gr['kv'], cap, gr['kv'], cap,
                                               gr['logits'], 1, sm, slot=slot, n_past_dev=counter, n_new=1, live_rows=gr['live'],
                                               not_alone=shared)
-                            self._greedy(st, lo, hi, gr['logits'].data_ptr(), V, 0, sm, n_past_dev=counter)
+                            token_step(gr, gr['logits'].data_ptr(), V, 0, sm, n_past_dev=counter)
                             finish_step(gr, counter)
                         st['graphs'][gkey], st['counters'][gkey] = graph, counter
                         st['counters'][gkey + ('fresh',)] = True
@@ -1032,8 +1255,8 @@ class WhisperDecoding:
                             gr['active'] = False
         for s_ in streams:
             main.wait_stream(s_)
-        out = self._finish_main_loop(st, cur, L0, n_batch, ignore_eot,
-                                     nsp_dev if self.tokenizer.no_speech is not None else None)
+        finish = self._finish_beam_loop if self.beam else self._finish_main_loop
+        out = finish(st, cur, L0, n_batch, ignore_eot, nsp_dev if self.tokenizer.no_speech is not None else None)
         self._rep_cache = None        # the candidates' repeated features (best_of): the language pass and this loop have both used them
         if one_row and not _retry and self._chain_gave_up("decode loop"):
             # one-row groups run the token step as ONE launch whose workgroups wait for each other with bounded spins; a wait that was
@@ -1126,6 +1349,21 @@ class WhisperDecoding:
         no_speech_probs = [np.nan] * n_batch
         if nsp_dev is not None:
             no_speech_probs = nsp_dev.tolist()
+        return tokens, st['sum_logprobs'].clone(), no_speech_probs
+
+    def _finish_beam_loop(self, st, cur, L0, n_batch, ignore_eot, nsp_dev):
+        """The beam loop's results: the live beams as the (tokens, sum_logprobs, no_speech_probs) triple, and the device's pools and
+        freeze lengths handed to `self.decoder`, whose `finalize` (post_process) then builds the candidates exactly as after the
+        literal loop."""
+        K = self.decoder.beam_size
+        tokens = st['tokens'][:, :cur].to(torch.int64)
+        count, length = st['fin_count'].tolist(), st['fin_len'].tolist()
+        scores, fin, live_len = st['fin_scores'].tolist(), st['fin_tokens'].cpu(), st['live_len'].tolist()
+        self.decoder.reset(n_batch // K)
+        for a in range(n_batch // K):
+            self.decoder.pool[a] = [(fin[a, e, :length[a][e]].tolist(), scores[a][e]) for e in range(count[a])]
+            self.decoder.live_len[a] = live_len[a] if live_len[a] > 0 else None
+        no_speech_probs = nsp_dev.tolist() if nsp_dev is not None else [np.nan] * n_batch
         return tokens, st['sum_logprobs'].clone(), no_speech_probs
 
     # ---- post-processing -------------------------------------------------------------------------------

@@ -79,6 +79,7 @@ EXPORTS = (
     "wm_profile_configure", "wm_profile_read", "wm_step_advance", "wm_log_mel_workspace_bytes", "wm_log_mel",
     "wm_flac_info", "wm_flac_decode", "wm_conv1d_gelu", "wm_argmax", "wm_gemv_fused", "wm_gemm_rows", "wm_set_rows_path", "wm_set_small_batch_rows", "wm_set_self_attn_waves", "wm_set_gemm_small_tiles", "wm_lab_knobs", "wm_set_cross_v_skip", "wm_set_decode_chain", "wm_decode_chain_error", "wm_decode_chain_status", "wm_debug_occupy", "wm_decoder_step_multi", "wm_stream_create_cu_mask", "wm_stream_destroy", "wm_attn_decode_cross_i8", "wm_debug_timeline",
     "wm_step_finish",
+    "wm_beam_workspace_bytes", "wm_beam_step", "wm_kv_reorder",
 )
 
 
@@ -173,6 +174,30 @@ class WmGreedyIO(C.Structure):
     ]
 
 
+class WmBeamIO(C.Structure):
+    """wm_beam_io (include/whisper_mi355.h)."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("row_stride", C.c_int64),
+        ("batch", C.c_int32), ("n_vocab", C.c_int32),
+        ("tokens", C.c_void_p), ("tokens_ld", C.c_int32), ("cur_len", C.c_int32),
+        ("sum_logprobs", C.c_void_p),
+        ("suppress", C.c_void_p), ("n_suppress", C.c_int32),
+        ("blank", C.c_void_p), ("n_blank", C.c_int32),
+        ("sample_begin", C.c_int32), ("eot", C.c_int32), ("timestamp_begin", C.c_int32),
+        ("max_initial_timestamp_index", C.c_int32),
+        ("apply_rules", C.c_int32),
+        ("beam_size", C.c_int32), ("max_candidates", C.c_int32), ("ignore_eot", C.c_int32),
+        ("n_past_dev", C.c_void_p),
+        ("row_limit", C.c_void_p),
+        ("parent", C.c_void_p),
+        ("fin_tokens", C.c_void_p), ("fin_scores", C.c_void_p), ("fin_len", C.c_void_p), ("fin_count", C.c_void_p),
+        ("live_len", C.c_void_p),
+        ("done", C.c_void_p),
+        ("n_done", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -247,6 +272,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_flac_decode.argtypes = [vp, sz, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.wm_step_advance.argtypes = [vp, vp]
     lib.wm_step_finish.argtypes = [vp, vp, i32, vp, vp]
+    lib.wm_beam_workspace_bytes.argtypes = [i32, i32]
+    lib.wm_beam_workspace_bytes.restype = sz
+    lib.wm_beam_step.argtypes = [C.POINTER(WmBeamIO), vp]
+    lib.wm_kv_reorder.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]
     lib.wm_debug_timeline.argtypes = [vp, i32]
     lib.wm_profile_configure.argtypes = [i32, i32, i32]
     lib.wm_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]

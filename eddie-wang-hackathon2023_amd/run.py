@@ -19,17 +19,23 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from decoding import WhisperDecoding
+from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 
 
-def parse_arguments():
+def parse_arguments(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--log_level', type=str, default='error')
     parser.add_argument('--engine_dir', type=str, default='whisper_outputs')
     parser.add_argument('--input_file', type=str, default='synthetic')
     parser.add_argument('--vocab', type=str, default=None, help='path to multilingual.tiktoken (text output)')
-    return parser.parse_args()
+    parser.add_argument('--beam_size', type=int, default=None, help='beam search with that many beams (1..8; default: greedy)')
+    parser.add_argument('--patience', type=float, default=None, help='beam search: finished candidates per utterance = beam_size * patience')
+    return parser.parse_args(argv)
+
+
+def decoding_options(args) -> DecodingOptions:
+    return DecodingOptions(beam_size=args.beam_size, patience=args.patience)
 
 
 def load_mel(input_file: str) -> torch.Tensor:
@@ -45,13 +51,13 @@ def load_mel(input_file: str) -> torch.Tensor:
 
 
 def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', input_file: str = 'synthetic',
-             vocab: str = None):
+             vocab: str = None, beam_size: int = None, patience: float = None):
     logging.basicConfig(level=getattr(logging, log_level.upper(), logging.ERROR))
     torch.cuda.set_device(0)
     mel = load_mel(input_file).to('cuda').type(torch.float16).unsqueeze(0)
     engine_dir = Path(engine_dir)
     whisper_encoding = WhisperEncoding(engine_dir)
-    whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab)
+    whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=DecodingOptions(beam_size=beam_size, patience=patience))
     begin_time = time.time()
     audio_features = whisper_encoding.get_audio_features(mel)
     languages, language_probs = whisper_decoding.detect_language(audio_features)

@@ -21,7 +21,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from decoding import WhisperDecoding
+from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 from normalizers import EnglishTextNormalizer
 from wer import wer as word_error_rate
@@ -296,7 +296,7 @@ def main(args) -> Optional[dict]:
     engine_dir = Path(args.engine_dir)
     only_torch = not args.test_trt_llm                 # the PyTorch path alone needs the engine directory's configuration, not its engines
     whisper_encoding = WhisperEncoding(engine_dir, only_torch=only_torch)
-    whisper_decoding = WhisperDecoding(engine_dir, only_torch=only_torch, vocab_path=args.vocab)
+    whisper_decoding = WhisperDecoding(engine_dir, only_torch=only_torch, vocab_path=args.vocab, options=decoding_options(args))
     if args.sample_len:
         whisper_decoding.sample_len = args.sample_len
     pairs = discover(args.dataset_dir)
@@ -343,7 +343,13 @@ def parse_arguments(argv=None):
     parser.add_argument('--sample_len', type=int, default=None, help='tokens sampled per utterance at most (default: n_text_ctx // 2)')
     parser.add_argument('--overlap_encoder', action='store_true',
                         help='run the encoder of the next batch beside the decode loop of the current one (eval_engines_stream)')
+    parser.add_argument('--beam_size', type=int, default=None, help='beam search with that many beams (1..8; default: greedy)')
+    parser.add_argument('--patience', type=float, default=None, help='beam search: finished candidates per utterance = beam_size * patience')
     return parser.parse_args(argv)
+
+
+def decoding_options(args) -> DecodingOptions:
+    return DecodingOptions(beam_size=args.beam_size, patience=args.patience)
 
 
 if __name__ == '__main__':

@@ -220,6 +220,55 @@ int wm_step_advance(int32_t* counter, wm_stream_t stream);
  * batch <= 1024. */
 int wm_step_finish(int32_t* counter, const int32_t* done, int batch, int32_t* live, wm_stream_t stream);
 
+/* ---- beam search step (added within ABI 8: new entries only, no existing struct or signature changed) ----------------
+ * The semantics of upstream Whisper's BeamSearchDecoder.update on the device, one call per token step of an utterance
+ * group.  Rows are n_audio x beam_size; beam j of utterance a is row a * beam_size + j.  Per utterance:
+ *   1. the logit filters of wm_greedy_step (same fields, same meaning) on every row's own history, log-softmax in fp32;
+ *   2. every beam proposes its beam_size + 1 best tokens (equal log-probabilities: lower token id first; tokens at -inf are
+ *      never proposed -- Whisper's rules always leave more than beam_size + 1 finite ones); score = sum_logprobs + logprob.
+ *      At the first sampled step (cur_len == sample_begin) the beams are identical and only beam 0 proposes;
+ *   3. candidates are walked by (score descending, parent beam ascending, token ascending).  One ending in EOT joins the
+ *      step's finished list, any other becomes the next live beam until beam_size are saved, where the walk stops;
+ *   4. live beam i takes its parent's token history plus the new token (moved in place), sum_logprobs[i] = the score and
+ *      parent[i] = the parent's row index within this launch (wm_kv_reorder moves the self-attention cache accordingly);
+ *   5. the finished candidates go to the utterance's pool (history + EOT, score, length), best first, while it holds
+ *      fewer than max_candidates.  A full pool completes the utterance: done[] of all its rows is set, n_done grows by
+ *      beam_size, live_len[a] = the live beams' length, and every later call leaves the utterance untouched (frozen;
+ *      parent = identity).  row_limit (per row, the beams of an utterance carry the same value): after that many sampled
+ *      tokens the utterance is frozen before the step.  ignore_eot: EOT candidates are pooled but nothing is frozen.
+ * Bounds: 1 <= beam_size <= 8, 1 <= max_candidates <= 16, batch a multiple of beam_size.                              */
+typedef struct wm_beam_io {
+    void* logits; int64_t row_stride;   /* as wm_greedy_io */
+    int32_t batch, n_vocab;             /* batch = rows = n_audio * beam_size */
+    int32_t* tokens; int32_t tokens_ld; int32_t cur_len;
+    float* sum_logprobs;
+    const int32_t* suppress; int32_t n_suppress;
+    const int32_t* blank; int32_t n_blank;
+    int32_t sample_begin, eot, timestamp_begin, max_initial_timestamp_index;
+    int32_t apply_rules;
+    int32_t beam_size, max_candidates, ignore_eot;
+    const int32_t* n_past_dev;          /* optional device step counter: cur_len = *n_past_dev + 1 */
+    const int32_t* row_limit;           /* optional int32 [batch] */
+    int32_t* parent;                    /* out, int32 [batch] */
+    int32_t* fin_tokens;                /* pool: int32 [n_audio, max_candidates, tokens_ld] */
+    float* fin_scores;                  /* float [n_audio, max_candidates] */
+    int32_t* fin_len;                   /* int32 [n_audio, max_candidates]: tokens of the entry, the closing EOT included */
+    int32_t* fin_count;                 /* int32 [n_audio], caller zeroes it */
+    int32_t* live_len;                  /* int32 [n_audio]: length of a frozen utterance's live beams (written when it freezes) */
+    int32_t* done;                      /* int32 [batch], caller zeroes it */
+    int32_t* n_done;                    /* optional int32 [1] */
+    void* workspace; size_t workspace_bytes;   /* >= wm_beam_workspace_bytes(batch, beam_size): the rows' proposals */
+} wm_beam_io;
+size_t wm_beam_workspace_bytes(int batch, int beam_size);
+int wm_beam_step(const wm_beam_io* io, wm_stream_t stream);
+/* The self-attention caches follow their beams: for every layer (layers_dev: n_layer DEVICE-resident pointers to
+ * [batch, 2, n_head, capacity, 64] of elem_bytes 1 (int8) or 2 (fp16)) row i receives row parent[i]'s positions 0 .. n_last,
+ * n_last = *n_past_dev when given.  In place: one workgroup owns the same slice of all beams of an utterance, loads, then
+ * stores.  Utterances whose parents are the identity or whose done[] is set (optional) are skipped; nothing beyond n_last
+ * is touched.  A parent outside its own utterance's rows is treated as the identity. */
+int wm_kv_reorder(void* const* layers_dev, int n_layer, int batch, int beam_size, int n_head, int capacity, int elem_bytes,
+                  const int32_t* parent, const int32_t* done, int n_last, const int32_t* n_past_dev, wm_stream_t stream);
+
 /* ---- kernel-level entry points (parity tests, micro-benchmarks, roofline measurement) -----------*/
 /* C[M,N] = act(A[M,K] x W[N,K]^T * scale + bias) (+ residual); W fp16 or int8 (w8) row-major [N][K].
  * act: 0 none, 1 erf-GELU, 2 tanh-GELU.  Replaces CutlassFpAIntBGemmRunner::gemm /
