@@ -191,6 +191,12 @@ __device__ __forceinline__ void lane_rows_swap16(uint32_t& a, uint32_t& b) {
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
 }
 __device__ __forceinline__ float r16(float x) { return (float)(h16)x; }   // round through fp16
+// The same rounding with the operand MATERIALISED as an fp32 value first.  Where the operand is a product, hipcc otherwise fuses
+// the multiply and the conversion into v_fma_mixlo_f16 in some instantiations of a kernel and not in others (a handful of a tile's
+// elements, even): that instruction rounds the exact product ONCE, multiply + convert round it twice, and the two differ wherever
+// the fp32 product lands on an fp16 tie.  The GEMM epilogues promise the same bits in every tile form, so they all round twice,
+// as the packed conversions of the persistent kernel's SIMPLE epilogue do.
+__device__ __forceinline__ float r16_f32(float x) { asm("" : "+v"(x)); return (float)(h16)x; }
 
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. far below an fp16 ulp of any GELU output that matters) on the
 // hardware reciprocal and exp2 (v_rcp_f32 / v_exp_f32, 1 ulp each -- inside the formula's own error): 14 instructions + 2

@@ -1325,6 +1325,76 @@ int wm_conv1d_gelu(const void* x_pad, int B, int T_in, int C_in, const void* W, 
     return launch_gemm_f16(p, (hipStream_t)stream);
 }
 
+// ---- test-only entries: the engines' own GemmBigParams / row-kernel options, reachable alone (tests/test_gpu_gemm_epilogue.py)
+int wm_gemm_ex(const wm_gemm_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io && io->a && io->w && io->c, "wm_gemm_ex: null argument");
+    WM_REQUIRE(io->m > 0 && io->n > 0 && io->k > 0, "wm_gemm_ex: empty shape m=%d n=%d k=%d", io->m, io->n, io->k);
+    WM_REQUIRE(io->n % 128 == 0, "wm_gemm_ex: n=%d must be a multiple of 128", io->n);
+    WM_REQUIRE(io->k % 64 == 0, "wm_gemm_ex: k=%d must be a multiple of 64", io->k);
+    WM_REQUIRE(io->act >= 0 && io->act <= 2, "wm_gemm_ex: act=%d (0 none, 1 erf-GELU, 2 tanh-GELU)", io->act);
+    WM_REQUIRE(io->lda % 8 == 0 && io->lda > 0, "wm_gemm_ex: lda=%d must be a positive multiple of 8", io->lda);
+    WM_REQUIRE(io->colscale_n >= 0 && io->colscale_n <= io->n && io->colscale_n % 4 == 0, "wm_gemm_ex: colscale_n=%d must be a multiple of 4 in [0, n]", io->colscale_n);
+    WM_REQUIRE(io->res_mod >= 0 && (!io->residual || (io->ldr >= io->n && io->ldr % 4 == 0)), "wm_gemm_ex: residual needs ldr >= n, a multiple of 4, and res_mod >= 0");
+    WM_REQUIRE(io->a_rows >= 0 && io->c_rows >= 0 && io->max_wgs >= 0 && io->tile_rows >= 0, "wm_gemm_ex: negative a_rows / c_rows / max_wgs / tile_rows");
+    WM_REQUIRE(io->out_mode == 0 || io->out_mode == 1, "wm_gemm_ex: out_mode=%d (0 row-major, 1 head-split)", io->out_mode);
+    if (io->out_mode == 1) {
+        WM_REQUIRE(io->hs_t > 0 && io->hs_h > 0 && io->m % io->hs_t == 0, "wm_gemm_ex: head-split needs hs_t > 0, hs_h > 0 and m a multiple of hs_t");
+        WM_REQUIRE(io->hs_kv <= 1 && io->n == (io->hs_kv < 0 ? 2 : 1) * io->hs_h * 64, "wm_gemm_ex: head-split n=%d does not match hs_h=%d, hs_kv=%d", io->n, io->hs_h, io->hs_kv);
+        WM_REQUIRE(io->c_rows == 0, "wm_gemm_ex: c_rows is for the row-major output only");
+    } else {
+        WM_REQUIRE(io->ldc >= io->n && io->ldc % 4 == 0, "wm_gemm_ex: ldc=%d must be a multiple of 4, >= n", io->ldc);
+        WM_REQUIRE(!(io->q8_inv_scale > 0.f), "wm_gemm_ex: q8_inv_scale is for the head-split output only");
+    }
+    GemmBigParams p{};
+    p.A = (const h16*)io->a; p.lda = io->lda; p.M = io->m; p.K = io->k; p.W = io->w; p.N = io->n;
+    p.bias = (const h16*)io->bias; p.C = (h16*)io->c; p.ldc = io->out_mode == 1 ? 0 : io->ldc;
+    p.residual = (const h16*)io->residual; p.ldr = io->residual ? io->ldr : 0; p.res_mod = io->res_mod; p.act = io->act;
+    p.colscale_n = io->colscale_n; p.colscale = io->colscale;
+    p.out_mode = io->out_mode; p.hs_T = io->hs_t; p.hs_H = io->hs_h; p.hs_kv = io->hs_kv; p.q8_inv_scale = io->q8_inv_scale;
+    p.a_rows = io->a_rows; p.a_bstride = (long)io->a_bstride; p.c_rows = io->c_rows; p.c_bstride = (long)io->c_bstride;
+    p.max_wgs = io->max_wgs; p.tile_rows = io->tile_rows;
+    return launch_gemm_f16(p, (hipStream_t)stream);
+}
+
+int wm_row_finish(const wm_row_finish_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io, "wm_row_finish: null argument");
+    WM_REQUIRE(io->mode >= 0 && io->mode <= 3, "wm_row_finish: mode=%d (0 .. 3)", io->mode);
+    WM_REQUIRE(io->m > 0 && io->n > 0, "wm_row_finish: empty shape m=%d n=%d", io->m, io->n);
+    if (io->mode != 2) {
+        WM_REQUIRE(io->part && io->ksplit >= 1 && io->ldp >= io->n, "wm_row_finish: mode %d needs part, ksplit >= 1 and ldp >= n", io->mode);
+        WM_REQUIRE(io->part_sstride >= 0 && io->part_sstride % 4 == 0, "wm_row_finish: part_sstride must be a non-negative multiple of 4");
+    }
+    if (io->mode != 1) WM_REQUIRE(io->x && io->ldx >= io->n, "wm_row_finish: mode %d needs x with ldx >= n", io->mode);
+    if (io->mode != 3) WM_REQUIRE(io->out && io->ldo >= io->n, "wm_row_finish: mode %d needs out with ldo >= n", io->mode);
+    if (io->mode == 0 || io->mode == 2) WM_REQUIRE(io->ln_gamma && io->ln_beta, "wm_row_finish: mode %d needs ln_gamma and ln_beta", io->mode);
+    if (io->mode == 1) WM_REQUIRE(io->gelu_kind == 1 || io->gelu_kind == 2, "wm_row_finish: gelu_kind=%d (1 erf, 2 tanh)", io->gelu_kind);
+    RowFinishParams p{};
+    p.part = io->part; p.ksplit = io->ksplit; p.M = io->m; p.N = io->n; p.ldp = io->mode == 2 ? 0 : io->ldp; p.part_sstride = (long)io->part_sstride;
+    p.bias = (const h16*)io->bias; p.mode = io->mode; p.gelu_kind = io->gelu_kind;
+    p.x = (h16*)io->x; p.ldx = io->mode == 1 ? 0 : io->ldx; p.ln_g = (const h16*)io->ln_gamma; p.ln_b = (const h16*)io->ln_beta;
+    p.out = (h16*)io->out; p.ldo = io->mode == 3 ? 0 : io->ldo;
+    return launch_row_finish(p, (hipStream_t)stream);
+}
+
+int wm_embed(const int32_t* tokens, int tokens_ld, int M, int L, const void* emb_tiles, int C, const void* pos,
+             void* x, int ldx, int n_vocab, const int32_t* t_dev, uint32_t* generation, wm_stream_t stream) {
+    WM_REQUIRE(tokens && emb_tiles && pos && x, "wm_embed: null argument");
+    WM_REQUIRE(M >= 1 && L >= 1 && M % L == 0 && tokens_ld >= L && n_vocab >= 1, "wm_embed: M=%d must be a multiple of L=%d >= 1, tokens_ld=%d >= L, n_vocab=%d >= 1", M, L, tokens_ld, n_vocab);
+    WM_REQUIRE(C >= 32 && ldx >= C && ldx % 8 == 0, "wm_embed: ldx=%d must be a multiple of 8, >= C=%d", ldx, C);
+    EmbedParams ep{tokens, tokens_ld, M, L, emb_tiles, C, (const h16*)pos, (h16*)x, ldx, n_vocab, t_dev, generation};
+    return launch_embed(ep, (hipStream_t)stream);
+}
+
+int wm_mel_transpose_pad(const void* mel, int B, int n_mels, int T, void* out, wm_stream_t stream) {
+    WM_REQUIRE(mel && out && B >= 1 && n_mels >= 1 && T >= 1, "wm_mel_transpose_pad: null argument or empty input");
+    return launch_mel_transpose_pad((const h16*)mel, B, n_mels, T, (h16*)out, (hipStream_t)stream);
+}
+
+int wm_zero_pad_rows(void* buf, int B, int Tpad, int C, wm_stream_t stream) {
+    WM_REQUIRE(buf && B >= 1 && Tpad >= 2 && C >= 1, "wm_zero_pad_rows: null argument or empty input");
+    return launch_zero_pad_rows((h16*)buf, B, Tpad, C, (hipStream_t)stream);
+}
+
 int wm_argmax(const void* logits, int64_t row_stride, int batch, int n_vocab, int32_t* ids, wm_stream_t stream) {
     WM_REQUIRE(logits && ids && batch >= 1 && n_vocab >= 1, "wm_argmax: null argument or empty input");
     return launch_argmax((const h16*)logits, (long)row_stride, batch, n_vocab, ids, (hipStream_t)stream);

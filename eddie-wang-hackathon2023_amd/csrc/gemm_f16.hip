@@ -168,24 +168,24 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void gemm_f16_kernel(GemmBigParams p
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[j][r] = r16(acc[i][j][r] + (float)b4[j][r]);      // the Linear's fp16 output
+            for (int r = 0; r < 4; ++r) v[j][r] = r16_f32(acc[i][j][r] + (float)b4[j][r]);      // the Linear's fp16 output
         if (ACT == 1) {
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[j][r] = r16(gelu_erf(v[j][r]));
+                for (int r = 0; r < 4; ++r) v[j][r] = r16_f32(gelu_erf(v[j][r]));
         } else if (ACT == 2) {
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[j][r] = r16(gelu_tanh(v[j][r]));
+                for (int r = 0; r < 4; ++r) v[j][r] = r16_f32(gelu_tanh(v[j][r]));
         }
         if (scale_cols) {                                           // q, k * d^-0.25 (torch_model.py:93-95)
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const float sc = (colw + j * 16 < p.colscale_n) ? p.colscale : 1.0f;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[j][r] = r16(v[j][r] * sc);
+                for (int r = 0; r < 4; ++r) v[j][r] = r16_f32(v[j][r] * sc);
             }
         }
         if (p.residual) {
@@ -241,7 +241,7 @@ int launch_gemm_f16(const GemmBigParams& p, hipStream_t stream) {
     WM_REQUIRE(p.N % 128 == 0, "gemm_f16: N=%d must be a multiple of 128", p.N);
     WM_REQUIRE(p.K % BK == 0, "gemm_f16: K=%d must be a multiple of %d", p.K, BK);
     WM_REQUIRE(p.lda % 8 == 0, "gemm_f16: lda=%d must be a multiple of 8 (16-byte loads)", p.lda);
-    WM_REQUIRE(p.ldc % 8 == 0 && p.ldr % 8 == 0, "gemm_f16: ldc/ldr must be multiples of 8 (16-byte epilogue accesses)");
+    WM_REQUIRE(p.ldc % 4 == 0 && p.ldr % 4 == 0, "gemm_f16: ldc/ldr must be multiples of 4 (8-byte epilogue accesses)");      // as gemm_f16p.hip: a shape must not be refused by one tile form and taken by the other
     WM_REQUIRE(p.M > 0, "gemm_f16: empty M");
     WM_REQUIRE(p.act >= 0 && p.act <= 2, "gemm_f16: act=%d", p.act);
     // 0: 256 x 256, 1: 256 x 128, 2: 128 x 128 (4 waves, two workgroups per CU), 3: 64 x 128 (2 waves) when even the 128 x 128 tiles

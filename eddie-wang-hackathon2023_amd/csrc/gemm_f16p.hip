@@ -280,7 +280,7 @@ __global__ __launch_bounds__(512) void gemm_f16p_kernel(GemmBigParams p) {
                     for (int j = 0; j < 4; ++j) {
                         const half4v b4 = *(const half4v*)(bias_lds + jh * 64 + j * 16);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[j][r] = r16(acc[i][jh * 4 + j][r] + (float)b4[r]);      // the Linear's fp16 output
+                        for (int r = 0; r < 4; ++r) v[j][r] = r16_f32(acc[i][jh * 4 + j][r] + (float)b4[r]);      // the Linear's fp16 output
                     }
                     if (ACT == 1) {
 #pragma unroll
@@ -288,20 +288,20 @@ __global__ __launch_bounds__(512) void gemm_f16p_kernel(GemmBigParams p) {
 #pragma unroll
                             for (int r = 0; r < 4; r += 2) {             // two values per packed fp32 instruction, same arithmetic
                                 const float2v y = gelu_erf2(float2v{v[j][r], v[j][r + 1]});
-                                v[j][r] = r16(y[0]); v[j][r + 1] = r16(y[1]);
+                                v[j][r] = r16_f32(y[0]); v[j][r + 1] = r16_f32(y[1]);
                             }
                     } else if (ACT == 2) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) v[j][r] = r16(gelu_tanh(v[j][r]));
+                            for (int r = 0; r < 4; ++r) v[j][r] = r16_f32(gelu_tanh(v[j][r]));
                     }
                     if (scale_cols) {                                           // q, k * d^-0.25 (torch_model.py:93-95)
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const float sc = (colp + j * 16 < p.colscale_n) ? p.colscale : 1.0f;
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) v[j][r] = r16(v[j][r] * sc);
+                            for (int r = 0; r < 4; ++r) v[j][r] = r16_f32(v[j][r] * sc);
                         }
                     }
                     if constexpr (RES) {

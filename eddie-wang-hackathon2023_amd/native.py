@@ -80,6 +80,7 @@ EXPORTS = (
     "wm_flac_info", "wm_flac_decode", "wm_conv1d_gelu", "wm_argmax", "wm_gemv_fused", "wm_gemm_rows", "wm_set_rows_path", "wm_set_small_batch_rows", "wm_set_self_attn_waves", "wm_set_gemm_small_tiles", "wm_lab_knobs", "wm_set_cross_v_skip", "wm_set_decode_chain", "wm_decode_chain_error", "wm_decode_chain_status", "wm_debug_occupy", "wm_decoder_step_multi", "wm_stream_create_cu_mask", "wm_stream_destroy", "wm_attn_decode_cross_i8", "wm_debug_timeline",
     "wm_step_finish",
     "wm_beam_workspace_bytes", "wm_beam_step", "wm_kv_reorder",
+    "wm_gemm_ex", "wm_row_finish", "wm_embed", "wm_mel_transpose_pad", "wm_zero_pad_rows",
 )
 
 
@@ -198,6 +199,37 @@ class WmBeamIO(C.Structure):
     ]
 
 
+class WmGemmIO(C.Structure):
+    """wm_gemm_io (include/whisper_mi355.h): the MFMA GEMM with every option the engines set (tests)."""
+    _fields_ = [
+        ("a", C.c_void_p), ("lda", C.c_int32), ("m", C.c_int32), ("k", C.c_int32),
+        ("w", C.c_void_p), ("n", C.c_int32),
+        ("bias", C.c_void_p),
+        ("c", C.c_void_p), ("ldc", C.c_int32),
+        ("residual", C.c_void_p), ("ldr", C.c_int32), ("res_mod", C.c_int32),
+        ("act", C.c_int32),
+        ("colscale_n", C.c_int32), ("colscale", C.c_float),
+        ("out_mode", C.c_int32), ("hs_t", C.c_int32), ("hs_h", C.c_int32), ("hs_kv", C.c_int32),
+        ("q8_inv_scale", C.c_float),
+        ("a_rows", C.c_int32), ("a_bstride", C.c_int64),
+        ("c_rows", C.c_int32), ("c_bstride", C.c_int64),
+        ("max_wgs", C.c_int32), ("tile_rows", C.c_int32),
+    ]
+
+
+class WmRowFinishIO(C.Structure):
+    """wm_row_finish_io (include/whisper_mi355.h): the row kernel of the split-K decode path (tests)."""
+    _fields_ = [
+        ("part", C.c_void_p), ("ksplit", C.c_int32), ("m", C.c_int32), ("n", C.c_int32), ("ldp", C.c_int32),
+        ("part_sstride", C.c_int64),
+        ("bias", C.c_void_p),
+        ("mode", C.c_int32), ("gelu_kind", C.c_int32),
+        ("x", C.c_void_p), ("ldx", C.c_int32),
+        ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p),
+        ("out", C.c_void_p), ("ldo", C.c_int32),
+    ]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -277,6 +309,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_beam_step.argtypes = [C.POINTER(WmBeamIO), vp]
     lib.wm_kv_reorder.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]
     lib.wm_debug_timeline.argtypes = [vp, i32]
+    lib.wm_gemm_ex.argtypes = [C.POINTER(WmGemmIO), vp]
+    lib.wm_row_finish.argtypes = [C.POINTER(WmRowFinishIO), vp]
+    lib.wm_embed.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp]
+    lib.wm_mel_transpose_pad.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.wm_zero_pad_rows.argtypes = [vp, i32, i32, i32, vp]
     lib.wm_profile_configure.argtypes = [i32, i32, i32]
     lib.wm_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
     _lib = lib

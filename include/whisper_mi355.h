@@ -288,6 +288,56 @@ int wm_gemm(const void* A, int lda, int M, int K, const void* W, int N, int w8, 
  * out fp16 [B][T_in/stride][C_out].                                                                 */
 int wm_conv1d_gelu(const void* x_pad, int B, int T_in, int C_in, const void* W, int K, const void* bias,
                    int C_out, int stride, int gelu, void* out, wm_stream_t stream);
+/* ---- test-only entries (added within ABI 8: new entries only): the options of the MFMA GEMM and the row kernels that only the
+ * engines set, reachable alone so that parity tests can hold each to one fp16 ulp (tests/test_gpu_gemm_epilogue.py,
+ * tests/test_gpu_row_kernels.py).  Not used by the product path.
+ * wm_gemm_ex: C = epilogue(A . W^T), W fp16 [n][k] row-major, with every option the encoder and the cross-K/V engine use:
+ *   v = fp16(sum + bias); v = fp16(act(v)); columns < colscale_n: v = fp16(v * colscale); v = fp16(v + residual[row % res_mod or row])
+ *   a_rows > 0: row m of A lives at a + (m / a_rows) * a_bstride + (m % a_rows) * lda (elements); c_rows / c_bstride: the same for C
+ *   out_mode 1: C is head-split [m / hs_t, 2, hs_h, hs_t, 64]; hs_kv < 0: n = 2 * hs_h * 64 and the K | V index is col / (hs_h * 64),
+ *     else n = hs_h * 64 and hs_kv (0 or 1) names the half; q8_inv_scale > 0 (head-split only): C holds int8 codes
+ *     sat_s8(rne(fp16 result * q8_inv_scale))
+ *   max_wgs > 0: the persistent kernel on at most that many workgroups; tile_rows > 0: its tile order (1 = plain row-major).
+ * n a multiple of 128, k of 64, lda of 8, ldc / ldr of 4, colscale_n of 4. */
+typedef struct wm_gemm_io {
+    const void* a; int32_t lda, m, k;
+    const void* w; int32_t n;
+    const void* bias;                    /* fp16 [n], may be NULL */
+    void* c; int32_t ldc;
+    const void* residual; int32_t ldr, res_mod;
+    int32_t act;                         /* 0 none, 1 erf-GELU, 2 tanh-GELU */
+    int32_t colscale_n; float colscale;
+    int32_t out_mode, hs_t, hs_h, hs_kv;
+    float q8_inv_scale;
+    int32_t a_rows; int64_t a_bstride;
+    int32_t c_rows; int64_t c_bstride;
+    int32_t max_wgs, tile_rows;
+} wm_gemm_io;
+int wm_gemm_ex(const wm_gemm_io* io, wm_stream_t stream);
+/* The row kernel behind every Linear of the big-batch split-K decode path: y16 = fp16(sum_s part[s][row][:] + bias), then
+ *   mode 0  x = fp16(x + y16) in place, out = LayerNorm(x) * ln_gamma + ln_beta      mode 1  out = fp16(gelu(y16)) (gelu_kind 1 erf, 2 tanh)
+ *   mode 2  out = LayerNorm(x) * ln_gamma + ln_beta only (no partial sums)             mode 3  x = fp16(x + y16) only
+ * part fp32 [ksplit][m][ldp], slabs part_sstride elements apart (0: m * ldp); bias may be NULL.  n a multiple of 4, <= 6144.
+ * Fewer than 64 rows run the latency form (eight slabs in flight, the GELU mode cut into column ranges), more the gentle one:
+ * the same bits per row. */
+typedef struct wm_row_finish_io {
+    const float* part; int32_t ksplit, m, n, ldp; int64_t part_sstride;
+    const void* bias;
+    int32_t mode, gelu_kind;
+    void* x; int32_t ldx;
+    const void* ln_gamma; const void* ln_beta;
+    void* out; int32_t ldo;
+} wm_row_finish_io;
+int wm_row_finish(const wm_row_finish_io* io, wm_stream_t stream);
+/* x[r] = fp16(E[token of row r] + pos[r % L + T]), r < M = B * L; token of row r = tokens[(r / L) * tokens_ld + r % L + T];
+ * T = *t_dev when given, else 0.  emb_tiles: the fp16 embedding in tile-linear layout (weight.py: tile_linear), C a multiple
+ * of 32; token ids are clamped to [0, n_vocab).  generation (optional): incremented once per call. */
+int wm_embed(const int32_t* tokens, int tokens_ld, int M, int L, const void* emb_tiles, int C, const void* pos,
+             void* x, int ldx, int n_vocab, const int32_t* t_dev, uint32_t* generation, wm_stream_t stream);
+/* mel fp16 [B][n_mels][T] -> out fp16 [B][T + 2][n_mels], rows 0 and T + 1 of every utterance zero. */
+int wm_mel_transpose_pad(const void* mel, int B, int n_mels, int T, void* out, wm_stream_t stream);
+/* zeroes rows 0 and Tpad - 1 of every utterance of buf fp16 [B][Tpad][C]. */
+int wm_zero_pad_rows(void* buf, int B, int Tpad, int C, wm_stream_t stream);
 /* ids[b] = arg-max of row b of fp16 logits (first index wins ties).  The decode loop itself uses
  * wm_greedy_step, which fuses this with Whisper's logit rules (apply_rules = 0: plain arg-max + append). */
 int wm_argmax(const void* logits, int64_t row_stride, int batch, int n_vocab, int32_t* ids, wm_stream_t stream);
