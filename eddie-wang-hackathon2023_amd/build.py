@@ -81,6 +81,9 @@ def parse_arguments(args=None):
     parser.add_argument('--int8_cross_kv', default=False, action="store_true",
                         help='BEYOND the reference (which keeps them fp16): store the cross-attention K/V as int8 codes, one scale '
                              'per layer from --quantize_dir (torch_whisper_convert.py -kv); halves the decode loop\'s HBM traffic')
+    parser.add_argument('--alignment_heads', type=str, default=None,
+                        help='word timestamps: the cross-attention heads to align on, "layer:head,layer:head,..." or the path of a JSON '
+                             'list of [layer, head] pairs; default: every head of the upper half of the decoder layers (upstream\'s default)')
     parser.add_argument('--synthetic', type=str, default=None, help='build from a seeded random-init checkpoint of this size')
     parser.add_argument('--seed', type=int, default=0)
     parser.add_argument('--gelu', type=str, default='erf', choices=['erf', 'tanh'])
@@ -157,6 +160,14 @@ def build_decoder(model, args):
         hidden_size=md['n_text_state'], vocab_size=md['n_vocab'], max_batch_size=args.max_batch_size,
         use_int8_kv_cache=bool(args.int8_kv_cache), use_int8_cross_kv=bool(args.int8_cross_kv), int8=bool(args.int8_kv_cache), fp8=False, timing_cache=None,
         opt_level=None, use_refit=False, strongly_typed=False)
+    heads = getattr(args, 'alignment_heads', None)
+    if heads:       # stored as [layer, head] pairs; absent = the default (timing.default_alignment_heads)
+        import timing
+        if os.path.exists(heads):
+            with open(heads) as f:
+                heads = json.load(f)
+        flat = timing.parse_alignment_heads(heads, md['n_text_layer'], md['n_text_head'])
+        builder_config['alignment_heads'] = [[i // md['n_text_head'], i % md['n_text_head']] for i in flat]
     tensors = load_decoder_weight(params, md['n_text_layer'], args.quantize_dir,
                                   use_weight_only=_wo(args), use_int8_kv_cache=args.int8_kv_cache, use_int8_cross_kv=args.int8_cross_kv)
     blob = W.serialize_engine_blob(W.ENGINE_DECODER, _flags(args, args.int8_kv_cache), md, tensors)

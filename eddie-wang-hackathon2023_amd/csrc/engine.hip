@@ -1182,6 +1182,40 @@ int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t str
     return g.end(s);
 }
 
+// wm_decoder_step on the launch-per-kernel path, with the cross-attention queries of the listed heads written to the tape: behind
+// the cq projection of a layer the sums wait in the workspace for the cross-attention kernel (split-K slabs, or one slab from the
+// fused forms), where the tap kernel reads them too, in that kernel's order (align.hip).
+int wm_decoder_step_tap(const wm_engine* e, const wm_decoder_io* io, const wm_tap_io* tap, wm_stream_t stream_) {
+    WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_step_tap: not a decoder engine");
+    WM_REQUIRE(io && tap && tap->q_tape && tap->heads && tap->n_heads >= 1, "wm_decoder_step_tap: null argument");
+    WM_REQUIRE(io->n_new >= 1 && io->n_new <= DEC_CHUNK && !io->n_past_dev, "wm_decoder_step_tap: n_new must be 1 .. %d, without a device step counter", DEC_CHUNK);
+    const int H = e->dims.n_text_head, n_layer = e->dims.n_text_layer;
+    WM_REQUIRE(H <= 64, "wm_decoder_step_tap: %d heads per layer (at most 64)", H);
+    WM_REQUIRE(io->n_past >= 0 && tap->capacity >= io->n_past + io->n_new, "wm_decoder_step_tap: tape capacity %d < n_past + n_new = %d", tap->capacity,
+               io->n_past + io->n_new);
+    for (int k = 0; k < tap->n_heads; ++k)
+        WM_REQUIRE(tap->heads[k] >= 0 && tap->heads[k] < n_layer * H && (k == 0 || tap->heads[k] > tap->heads[k - 1]),
+                   "wm_decoder_step_tap: heads must be strictly ascending and below n_text_layer * n_text_head (entry %d = %d)", k, tap->heads[k]);
+    hipStream_t s = (hipStream_t)stream_;
+    GroupStep g;
+    if (int rc = g.init(e, io, s, false)) return rc;
+    if (g.begin(s)) return 2;
+    int k = 0;
+    for (int i = 0; i < n_layer; ++i) {
+        if (g.pre_cross(i, s)) return 2;
+        int heads[64], slots[64], n = 0;
+        for (; k < tap->n_heads && tap->heads[k] / H == i; ++k) { heads[n] = tap->heads[k] % H; slots[n] = k; ++n; }
+        if (n > 0) {
+            const Lin& cq = e->dec[i].cq;
+            if (int rc = launch_tap_q(g.w.part, g.cq_ks, cq.N, (long)g.M * cq.N, cq.b, g.B, g.L, g.T, (h16*)tap->q_tape, tap->n_heads,
+                                      tap->capacity, heads, slots, n, s)) return rc;
+        }
+        if (g.cross(i, s)) return 2;
+        if (g.post_cross(i, s)) return 2;
+    }
+    return g.end(s);
+}
+
 int wm_decoder_step_multi(const wm_engine* e, int n_groups, const wm_decoder_io* const* ios,
                           const wm_stream_t* light_streams, wm_stream_t heavy_stream) {
     WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_step_multi: not a decoder engine");

@@ -260,4 +260,10 @@ int launch_log_mel(const float* audio, int batch, int n_samples, long audio_ld, 
 
 int launch_quantize_i8(const h16* x, int8_t* q, long n, float inv_scale, hipStream_t stream);
 
+// ---------------------------------------------------------------- align.hip
+// The cross-attention query tap of wm_decoder_step_tap: r16(split-K slabs + bias) of `n` heads of one layer (heads_in_layer: head
+// index within the layer, slots: its place in the tape fp16 [B][n_tape_heads][capacity][64]), rows T .. T + L of every utterance.
+int launch_tap_q(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, int T, h16* tape,
+                 int n_tape_heads, int capacity, const int* heads_in_layer, const int* slots, int n, hipStream_t stream);
+
 }  // namespace wm

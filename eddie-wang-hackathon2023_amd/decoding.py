@@ -40,6 +40,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 import native
+import timing
 from build import get_engine_name
 from session import Session, TensorInfo, str_dtype_to_trt, trt_dtype_to_torch, logger
 from tokenizer import LANGUAGES, TO_LANGUAGE_CODE, Tokenizer
@@ -406,6 +407,9 @@ class WhisperDecoding:
         self.first_token_event = None     # bench.py: an event recorded (current stream) when the first sampled token of a main_loop call exists
         self._streams = []
         self._no_dedicated_queues = False
+        self._decode_in_flight = 0        # main_loop calls under way (word_timestamps reuses the loop's buffers)
+        self.last_alignment = None        # word_timestamps: the device's paths of the last call (and the matrices, with keep_alignment_matrix)
+        self.keep_alignment_matrix = False
         WhisperDecoding._instances.add(self)      # (weak: a give-up of a one-launch step drops the graphs of EVERY instance, _chain_gave_up)
 
     # ---- configuration / sessions -----------------------------------------------------------------
@@ -1061,6 +1065,15 @@ class WhisperDecoding:
                                        cur_len - 1, io.n_past_dev, stream), "wm_kv_reorder")
 
     def main_loop(self, audio_features, ignore_eot: bool = False, row_limit=None, _retry: bool = False):
+        """`_main_loop` with the in-flight mark around it: word_timestamps reuses the loop's buffers and refuses to run inside it
+        (a callback, another thread); the mark is cleared however the loop ends."""
+        self._decode_in_flight += 1
+        try:
+            return self._main_loop(audio_features, ignore_eot=ignore_eot, row_limit=row_limit, _retry=_retry)
+        finally:
+            self._decode_in_flight -= 1
+
+    def _main_loop(self, audio_features, ignore_eot: bool = False, row_limit=None, _retry: bool = False):
         """Greedy decoding, fast path.  Same return values as the reference's main_loop
         (tokens int64 [n, <=n_text_ctx+1], sum_logprobs fp32 [n], no_speech_probs list).
         `ignore_eot` (benchmarks with random weights) decodes `sample_len` tokens regardless.
@@ -1365,6 +1378,165 @@ class WhisperDecoding:
             self.decoder.live_len[a] = live_len[a] if live_len[a] > 0 else None
         no_speech_probs = nsp_dev.tolist() if nsp_dev is not None else [np.nan] * n_batch
         return tokens, st['sum_logprobs'].clone(), no_speech_probs
+
+    # ---- word-level timestamps (timing.py states the contract; DESIGN.md "word timestamps") ---------------------------------
+    def alignment_heads(self) -> List[int]:
+        """The cross-attention heads to align on, as layer * n_head + head, ascending: the engine's `alignment_heads`
+        (build.py --alignment_heads) or upstream's default, every head of the upper half of the decoder layers."""
+        cfg = self.decoder_config
+        return timing.parse_alignment_heads(cfg.get('alignment_heads'), cfg['num_layers'], cfg['num_heads'])
+
+    def _forced_tokens(self, sampled: Sequence[int]) -> Tuple[List[int], List[int]]:
+        """(text, forced sequence) of one utterance: the sampled tokens without the timestamp tokens, and
+        sot_sequence + <|notimestamps|> + text + <|endoftext|> -- no prompt, no prefix, as upstream."""
+        tk = self.tokenizer
+        text = [int(t) for t in sampled if int(t) < tk.eot]
+        return text, list(tk.sot_sequence) + [tk.no_timestamps] + text + [tk.eot]
+
+    def _split_words(self, tokens: List[int], language: Optional[str]):
+        """Words of `tokens` under the utterance's own language (the tokenizer carries the engine's default one)."""
+        return self.tokenizer.split_to_word_tokens(tokens, language=language)
+
+    def _align_frames(self, num_frames, n_audio) -> List[int]:
+        """F per utterance: half the mel frames of real audio, at most n_audio_ctx (the default: the whole window)."""
+        ctx = self.decoder_config['num_audio_ctx']
+        if num_frames is None:
+            return [ctx] * n_audio
+        frames = [int(f) for f in (num_frames.tolist() if hasattr(num_frames, 'tolist') else num_frames)]
+        if len(frames) != n_audio:
+            raise ValueError(f"word timestamps: {len(frames)} num_frames for {n_audio} utterances")
+        return [max(0, min(f, 2 * ctx)) // 2 for f in frames]
+
+    @staticmethod
+    def _result_tokens(results) -> List[List[int]]:
+        return [list(r.tokens) if hasattr(r, 'tokens') else [int(t) for t in r] for r in results]
+
+    def torch_word_timestamps(self, model, audio_features, tokens, num_frames=None) -> List[List[timing.WordTiming]]:
+        """The literal statement of the word-timestamp contract, on the PyTorch model (any device, any dtype of the features):
+        one teacher-forced `model.decoder` pass per utterance with the cross-attention scores captured, then timing.py's steps.
+        `tokens`: per utterance the sampled tokens (or the DecodingResults of post_process); `num_frames`: mel frames of real
+        audio per utterance (default: the whole window).  Differences from upstream: Z = 0 where a frame's weights have no
+        spread over the tokens (upstream: NaN), and none of the long-form duration heuristics."""
+        languages = [getattr(r, 'language', None) for r in tokens]
+        tokens = self._result_tokens(tokens)
+        frames = self._align_frames(num_frames, len(tokens))
+        heads, n_head = self.alignment_heads(), self.decoder_config['num_heads']
+        n_prefix, eot = len(self.tokenizer.sot_sequence), self.tokenizer.eot
+        seconds_per_frame = CHUNK_LENGTH / self.decoder_config['num_audio_ctx']
+        out, kept = [], []
+        for b, sampled in enumerate(tokens):
+            text, forced = self._forced_tokens(sampled)
+            if not text or frames[b] < 1:
+                out.append([])
+                kept.append(None)
+                continue
+            scores: List[Tensor] = []
+            with torch.no_grad():
+                x = torch.tensor([forced], dtype=torch.long, device=audio_features.device)
+                logits = model.decoder(x, audio_features[b:b + 1], cross_scores=scores)[0]
+            S_list = [scores[i // n_head][0, i % n_head, :, :frames[b]].float().cpu() for i in heads]
+            mtx = timing.alignment_matrix(S_list, n_prefix)
+            text_idx, time_idx = timing.dtw_cpu(-mtx.numpy())
+            probs = logits[n_prefix:, :eot].float().softmax(dim=-1).cpu()
+            token_probs = probs[torch.arange(len(text)), torch.tensor(text)].tolist()
+            words, word_tokens = self._split_words(text + [eot], languages[b])
+            out.append(timing.words_from_path(text_idx, time_idx, words, word_tokens, token_probs, seconds_per_frame))
+            kept.append(dict(scores=S_list, matrix=mtx, path_text=text_idx, path_time=time_idx, token_probs=token_probs))
+        self.last_alignment = kept
+        return out
+
+    def word_timestamps(self, audio_features, results, num_frames=None) -> List[List[timing.WordTiming]]:
+        """When each word of `results` (the DecodingResults of post_process for `audio_features`) was spoken: upstream
+        Whisper's find_alignment on the device.  A second, teacher-forced pass over sot_sequence + <|notimestamps|> + text + EOT
+        (4 tokens per call, wm_decoder_step_tap) records the cross-attention queries of the alignment heads; wm_align turns
+        them and the cross K/V that main_loop left in place into the alignment matrix and its DTW path; timing.words_from_path
+        reads the word boundaries off the path.  The pass reuses main_loop's cross K/V (same features: nothing is recomputed)
+        and its self-attention cache buffers, so no decode may be in flight.  `num_frames`: mel frames of real audio per
+        utterance (default: the whole window).  Beam search / best_of (n_group > 1) is not supported here in this version
+        (their rows' cross K/V are interleaved per candidate): use torch_word_timestamps."""
+        if self.n_group > 1:
+            raise ValueError("word_timestamps: beam_size / best_of > 1 is not supported on the device path in this version "
+                             "(torch_word_timestamps has no such limit)")
+        if self.use_int8_cross_kv:
+            raise native.WmError("word timestamps need fp16 cross-attention K/V; this engine stores int8 codes (WM_FLAG_INT8_CROSS_KV)")
+        if self._decode_in_flight:
+            raise RuntimeError("word_timestamps reuses main_loop's buffers: no decode may be in flight")
+        if not audio_features.is_cuda:
+            raise ValueError("word_timestamps runs on the GPU (torch_word_timestamps is the CPU statement)")
+        dev = audio_features.device
+        cfg = self.decoder_config
+        n, V, cap, ctx = audio_features.shape[0], cfg['vocab_size'], cfg['num_text_ctx'], cfg['num_audio_ctx']
+        sampled = self._result_tokens(results)
+        if len(sampled) != n:
+            raise ValueError(f"word_timestamps: {len(sampled)} results for {n} utterances")
+        languages = [getattr(r, 'language', None) for r in results]
+        tk = self.tokenizer
+        eot, n_prefix = tk.eot, len(tk.sot_sequence)
+        forced = [self._forced_tokens(s) for s in sampled]
+        frames = self._align_frames(num_frames, n)
+        n_all = [len(f) if t else 0 for t, f in forced]          # no text: no words, nothing to align (n_tokens - n_prefix - 1 < 1)
+        L = max(max(len(f) for _, f in forced), 1)
+        if L > cap:
+            raise ValueError(f"word_timestamps: a forced sequence of {L} tokens exceeds n_text_ctx = {cap}")
+        rows = torch.full((n, L + 1), eot, dtype=torch.int32)
+        for b, (_, f) in enumerate(forced):
+            rows[b, :len(f)] = torch.tensor(f, dtype=torch.int32)
+        rows = rows.to(dev)
+        heads = self.alignment_heads()
+        heads_arr = (C.c_int32 * len(heads))(*heads)
+        lib, sess, pos = native.load_library(), self.decoder_session, self.positional_embedding
+        st = self._fast_state(n, dev)
+        cross = self._cross_persistent(audio_features, st)
+        stream = torch.cuda.current_stream().cuda_stream
+        tape = torch.empty((n, len(heads), L, 64), dtype=torch.float16, device=dev)
+        logits = torch.empty(n * 4 * V, dtype=torch.float16, device=dev)
+        probs = torch.zeros((n, L), dtype=torch.float32, device=dev)
+        _, bounds = self._groups(n)
+        for g, (lo, hi) in enumerate(bounds):
+            kv, cr = [t[lo:hi] for t in st['kv']], [t[lo:hi] for t in cross]
+            for off in range(0, L, 4):
+                l = min(4, L - off)
+                lg = logits[: (hi - lo) * l * V].view(hi - lo, l, V)
+                sess.decoder_step_tap(rows[lo:hi, off:off + l], pos[off:off + l], cr, kv if off else None, cap, kv, cap, lg, off,
+                                      stream, tape[lo:hi], heads_arr, slot=1000 + g)
+                # the probability the pass gives the token that follows, over the text tokens only ([:eot]); no [B, L, V] tensor
+                lf = lg[:, :, :eot].float()
+                nxt = rows[lo:hi, off + 1: off + l + 1].long().clamp(max=eot - 1)
+                probs[lo:hi, off:off + l] = (lf.gather(-1, nxt[..., None])[..., 0] - lf.logsumexp(dim=-1)).exp()
+        n_tokens = torch.tensor(n_all, dtype=torch.int32, device=dev)
+        n_frames = torch.tensor(frames, dtype=torch.int32, device=dev)
+        path_ld = L + ctx
+        path_text = torch.zeros((n, path_ld), dtype=torch.int32, device=dev)
+        path_time = torch.zeros((n, path_ld), dtype=torch.int32, device=dev)
+        path_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        matrix = torch.zeros((n, L, ctx), dtype=torch.float32, device=dev) if self.keep_alignment_matrix else None
+        ws = torch.empty(max(256, lib.wm_align_workspace_bytes(n, len(heads), L, ctx)), dtype=torch.uint8, device=dev)
+        io = native.WmAlignIO()
+        io.engine = sess.engine.handle
+        io.batch, io.n_text_head, io.n_audio_ctx = n, cfg['num_heads'], ctx
+        io.q_tape, io.capacity = tape.data_ptr(), L
+        cross_arr = native.ptr_array(cross)
+        io.cross, io.n_layers = C.cast(cross_arr, C.POINTER(C.c_void_p)), cfg['num_layers']
+        io.heads, io.n_heads = C.cast(heads_arr, C.POINTER(C.c_int32)), len(heads)
+        io.n_tokens, io.n_frames = n_tokens.data_ptr(), n_frames.data_ptr()
+        io.n_prefix, io.filter_width, io.cap_tokens = n_prefix, timing.MEDIAN_FILTER_WIDTH, L
+        io.matrix, io.ld = (matrix.data_ptr(), ctx) if matrix is not None else (None, 0)
+        io.path_text, io.path_time, io.path_len = path_text.data_ptr(), path_time.data_ptr(), path_len.data_ptr()
+        io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
+        native.check(lib.wm_align(C.byref(io), stream), "wm_align")
+        lens = path_len.cpu().tolist()          # (synchronises: the workspace and the tape stay alive until here)
+        pt, pf, probs = path_text.cpu().numpy(), path_time.cpu().numpy(), probs.cpu()
+        self.last_alignment = dict(path_text=pt, path_time=pf, path_len=lens, n_tokens=n_all, n_frames=frames,
+                                   matrix=matrix.cpu() if matrix is not None else None, token_probs=probs)
+        out = []
+        for b, (text, _) in enumerate(forced):
+            if not text or lens[b] == 0:
+                out.append([])
+                continue
+            words, word_tokens = self._split_words(text + [eot], languages[b])
+            out.append(timing.words_from_path(pt[b, :lens[b]], pf[b, :lens[b]], words, word_tokens,
+                                              probs[b, n_prefix: n_prefix + len(text)].tolist(), CHUNK_LENGTH / ctx))
+        return out
 
     # ---- post-processing -------------------------------------------------------------------------------
     def compression_ratio(self, text) -> float:

@@ -81,6 +81,7 @@ EXPORTS = (
     "wm_step_finish",
     "wm_beam_workspace_bytes", "wm_beam_step", "wm_kv_reorder",
     "wm_gemm_ex", "wm_row_finish", "wm_embed", "wm_mel_transpose_pad", "wm_zero_pad_rows",
+    "wm_decoder_step_tap", "wm_align_workspace_bytes", "wm_align", "wm_dtw_workspace_bytes", "wm_dtw",
 )
 
 
@@ -230,6 +231,30 @@ class WmRowFinishIO(C.Structure):
     ]
 
 
+class WmTapIO(C.Structure):
+    """wm_tap_io (include/whisper_mi355.h): where wm_decoder_step_tap writes the cross-attention queries."""
+    _fields_ = [("q_tape", C.c_void_p), ("capacity", C.c_int32), ("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32)]
+
+
+class WmAlignIO(C.Structure):
+    """wm_align_io (include/whisper_mi355.h): alignment matrix + DTW of a batch (word timestamps)."""
+    _fields_ = [
+        ("engine", C.c_void_p),
+        ("batch", C.c_int32), ("n_text_head", C.c_int32), ("n_audio_ctx", C.c_int32),
+        ("q_tape", C.c_void_p), ("capacity", C.c_int32),
+        ("cross", C.POINTER(C.c_void_p)), ("n_layers", C.c_int32),
+        ("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32),
+        ("n_tokens", C.c_void_p),
+        ("n_frames", C.c_void_p),
+        ("n_prefix", C.c_int32), ("filter_width", C.c_int32),
+        ("cap_tokens", C.c_int32),
+        ("matrix", C.c_void_p), ("ld", C.c_int32),
+        ("path_text", C.c_void_p), ("path_time", C.c_void_p),
+        ("path_len", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -314,6 +339,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_embed.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp]
     lib.wm_mel_transpose_pad.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.wm_zero_pad_rows.argtypes = [vp, i32, i32, i32, vp]
+    lib.wm_decoder_step_tap.argtypes = [vp, C.POINTER(WmDecoderIO), C.POINTER(WmTapIO), vp]
+    lib.wm_align_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.wm_align_workspace_bytes.restype = sz
+    lib.wm_align.argtypes = [C.POINTER(WmAlignIO), vp]
+    lib.wm_dtw_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.wm_dtw_workspace_bytes.restype = sz
+    lib.wm_dtw.argtypes = [vp, i32, C.c_int64, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]
     lib.wm_profile_configure.argtypes = [i32, i32, i32]
     lib.wm_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
     _lib = lib

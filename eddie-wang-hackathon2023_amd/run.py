@@ -31,6 +31,8 @@ def parse_arguments(argv=None):
     parser.add_argument('--vocab', type=str, default=None, help='path to multilingual.tiktoken (text output)')
     parser.add_argument('--beam_size', type=int, default=None, help='beam search with that many beams (1..8; default: greedy)')
     parser.add_argument('--patience', type=float, default=None, help='beam search: finished candidates per utterance = beam_size * patience')
+    parser.add_argument('--word_timestamps', default=False, action='store_true',
+                        help='print "start-end word (probability)" lines after the text (cross-attention alignment + DTW on the device; greedy decoding only)')
     return parser.parse_args(argv)
 
 
@@ -50,8 +52,17 @@ def load_mel(input_file: str) -> torch.Tensor:
     return whisper_utils.log_mel_spectrogram_device(torch.from_numpy(audio).float().cuda(), dtype=torch.float32)
 
 
+def real_mel_frames(input_file: str):
+    """Mel frames of real audio in the 30-second window (None: unknown, the whole window counts) -- what the alignment of
+    --word_timestamps is restricted to."""
+    if input_file == 'synthetic' or input_file.endswith('.npy'):
+        return None
+    import whisper_utils
+    return min(len(whisper_utils.load_audio(input_file)) // whisper_utils.HOP_LENGTH, whisper_utils.N_FRAMES)
+
+
 def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', input_file: str = 'synthetic',
-             vocab: str = None, beam_size: int = None, patience: float = None):
+             vocab: str = None, beam_size: int = None, patience: float = None, word_timestamps: bool = False):
     logging.basicConfig(level=getattr(logging, log_level.upper(), logging.ERROR))
     torch.cuda.set_device(0)
     mel = load_mel(input_file).to('cuda').type(torch.float16).unsqueeze(0)
@@ -66,6 +77,11 @@ def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', inpu
     print("transcribe time " + str(time.time() - begin_time))
     result = result[0]
     print(result.text)
+    if word_timestamps:
+        frames = real_mel_frames(input_file)
+        words = whisper_decoding.word_timestamps(audio_features, [result], None if frames is None else [frames])[0]
+        for w in words:
+            print(f"{w.start:.2f}\u2013{w.end:.2f} {w.word.strip()} ({w.probability:.2f})")
     return result
 
 

@@ -260,6 +260,18 @@ class Session(object):
                                   qkv_amax, slot, n_past_dev, n_new, live_rows, not_alone)
         check(self._engine.lib.wm_decoder_step(self._engine.handle, C.byref(io), stream), "wm_decoder_step")
 
+    def decoder_step_tap(self, tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past, stream: int,
+                         q_tape: torch.Tensor, heads, slot: int = 0):
+        """wm_decoder_step_tap: the step on the launch-per-kernel path, with the cross-attention queries of `heads` (a ctypes
+        int32 array of layer * n_head + head, ascending) written to rows n_past .. of q_tape fp16 [B, len(heads), capacity, 64]."""
+        io = self.make_decoder_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
+                                  None, slot, None, None, None, True)
+        assert q_tape.dtype == torch.float16 and q_tape.is_contiguous() and q_tape.shape[0] == tokens.shape[0] and q_tape.shape[1] == len(heads)
+        tap = native.WmTapIO()
+        tap.q_tape, tap.capacity = q_tape.data_ptr(), q_tape.shape[2]
+        tap.heads, tap.n_heads = C.cast(heads, C.POINTER(C.c_int32)), len(heads)
+        check(self._engine.lib.wm_decoder_step_tap(self._engine.handle, C.byref(io), C.byref(tap), stream), "wm_decoder_step_tap")
+
     def decoder_step_multi(self, ios: Sequence[WmDecoderIO], light_streams: Sequence[int], heavy_stream: int):
         """One decode step of several utterance groups, interleaved layer by layer (wm_decoder_step_multi):
         each group's short kernels on its own light stream, all cross-attention kernels on `heavy_stream`."""

@@ -247,6 +247,49 @@ class Tokenizer:
         flush()
         return "".join(out)
 
+    # -- words (word-level timestamps, timing.py) -----------------------------------------------
+    def split_tokens_on_unicode(self, tokens: Sequence[int]) -> Tuple[List[str], List[List[int]]]:
+        """Cut `tokens` wherever the tokens so far decode to whole unicode characters: a multi-byte character that spans
+        tokens stays in one piece.  A U+FFFD that the text really contains (it is there in the decoding of the whole
+        sequence, at the same place) does not hold a piece open."""
+        whole = self.decode_with_timestamps(tokens)
+        pieces, piece_tokens, pending, offset = [], [], [], 0
+        for t in tokens:
+            pending.append(int(t))
+            text = self.decode_with_timestamps(pending)
+            bad = text.find("�")
+            if bad < 0 or whole[offset + bad: offset + bad + 1] == "�":
+                pieces.append(text)
+                piece_tokens.append(pending)
+                offset += len(text)
+                pending = []
+        return pieces, piece_tokens
+
+    def split_tokens_on_spaces(self, tokens: Sequence[int]) -> Tuple[List[str], List[List[int]]]:
+        """Unicode pieces glued into words: a piece opens a word when it is a special token, starts with a space or is a
+        punctuation mark; anything else continues the word before it."""
+        import string
+        pieces, piece_tokens = self.split_tokens_on_unicode(tokens)
+        words, word_tokens = [], []
+        for piece, toks in zip(pieces, piece_tokens):
+            opens = toks[0] >= self.eot or piece.startswith(" ") or piece.strip() in string.punctuation
+            if opens or not words:
+                words.append(piece)
+                word_tokens.append(list(toks))
+            else:
+                words[-1] += piece
+                word_tokens[-1] += toks
+        return words, word_tokens
+
+    def split_to_word_tokens(self, tokens: Sequence[int], language: Optional[str] = None) -> Tuple[List[str], List[List[int]]]:
+        """(words, their tokens).  Languages written without spaces are cut at unicode characters only (`language`: the
+        utterance's, default the tokenizer's own); without a vocabulary (ids-only mode) every token is its own word."""
+        if self.bpe is None:
+            return [self.decode_with_timestamps([t]) for t in tokens], [[int(t)] for t in tokens]
+        if (language or self.language) in {"zh", "ja", "th", "lo", "my", "yue"}:
+            return self.split_tokens_on_unicode(tokens)
+        return self.split_tokens_on_spaces(tokens)
+
     @cached_property
     def non_speech_tokens(self) -> Tuple[int, ...]:
         """Tokens for speaker tags / non-speech annotations (reference tokenizer.py:215-251):

@@ -179,11 +179,27 @@ class Whisper:
 
     embed_audio = encoder
 
-    def decoder(self, tokens: Tensor, audio_features: Tensor, kv_cache: Optional[dict] = None) -> Tensor:
+    @staticmethod
+    def cross_attention_scores(q: Tensor, k: Tensor, n_head: int) -> Tensor:
+        """The cross-attention scores as the alignment contract states them (timing.py; the engine's arithmetic up to the
+        score, csrc/attn_decode.hip): q16 = r16(r16(q) * hs^-0.25), k16 = r16(r16(k) * hs^-0.25) per head, S = q16 . k16 in fp32,
+        not rounded again.  q [B, L, C], k [B, Tk, C] -> fp32 [B, n_head, L, Tk]."""
+        b, n_q, c = q.shape
+        s = torch.tensor((c // n_head) ** -0.25, dtype=torch.float32)
+
+        def r16(x):
+            return x.to(torch.float16).float()
+        qh = r16(r16(q) * s).reshape(b, n_q, n_head, -1).transpose(1, 2)
+        kh = r16(r16(k) * s).reshape(b, k.shape[1], n_head, -1).permute(0, 2, 3, 1)
+        return qh @ kh
+
+    def decoder(self, tokens: Tensor, audio_features: Tensor, kv_cache: Optional[dict] = None,
+                cross_scores: Optional[list] = None) -> Tensor:
         """tokens [B, L] (all of them on the first call, the newest one afterwards when `kv_cache` is given), audio features
         [B, n_audio_ctx, C] -> fp32 logits [B, L, n_vocab] (W/torch_model.py:191-214).  `kv_cache` (the dict of
         `install_kv_cache_hooks`) keeps every layer's self-attention keys / values, appended call by call, and the cross-attention
-        keys / values of the first call."""
+        keys / values of the first call.  `cross_scores` (a list, optional): every layer appends its cross-attention scores,
+        fp32 [B, n_head, L, n_audio_ctx] (`Whisper.cross_attention_scores`), for word-level timestamps; the pass itself is unchanged."""
         d, p = self.dims, self.p
         cache = kv_cache if kv_cache is not None else {}
         offset = cache["dec.0.self.k"].shape[1] if "dec.0.self.k" in cache else 0
@@ -206,7 +222,10 @@ class Whisper:
                     cache[f"dec.{i}.cross.k"], cache[f"dec.{i}.cross.v"] = ck, cv
             else:
                 ck, cv = cache[f"dec.{i}.cross.k"], cache[f"dec.{i}.cross.v"]
-            x = x + self._linear(pre + ".cross_attn.out", self._attend(self._linear(pre + ".cross_attn.query", h), ck, cv, d.n_text_head, None))
+            cq = self._linear(pre + ".cross_attn.query", h)
+            if cross_scores is not None:
+                cross_scores.append(self.cross_attention_scores(cq, ck, d.n_text_head))
+            x = x + self._linear(pre + ".cross_attn.out", self._attend(cq, ck, cv, d.n_text_head, None))
             x = x + self._mlp(pre, x)
         x = self._norm("decoder.ln", x)
         return (x @ p["decoder.token_embedding.weight"].to(x.dtype).transpose(0, 1)).float()

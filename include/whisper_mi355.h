@@ -269,6 +269,58 @@ int wm_beam_step(const wm_beam_io* io, wm_stream_t stream);
 int wm_kv_reorder(void* const* layers_dev, int n_layer, int batch, int beam_size, int n_head, int capacity, int elem_bytes,
                   const int32_t* parent, const int32_t* done, int n_last, const int32_t* n_past_dev, wm_stream_t stream);
 
+/* ---- word-level timestamps (added within ABI 8: new entries only, no existing struct or signature changed) ------------
+ * Upstream Whisper's find_alignment on the device: a teacher-forced pass that records the cross-attention queries of the
+ * alignment heads (wm_decoder_step_tap), then softmax over frames, z-score over tokens, median filter over frames, mean over
+ * heads and dynamic time warping (wm_align).  DESIGN.md "word timestamps" states the contract; timing.py is its host form.
+ *
+ * wm_decoder_step_tap = wm_decoder_step for n_new <= 4 on the launch-per-kernel path (as if io->not_alone were set; n_past_dev
+ * must be NULL).  Behind the cross-attention query projection of every layer that has a listed head, one small kernel adds the
+ * split-K slabs and the bias in the cross-attention kernel's own order and writes r16(q_sum + bias) -- the query BEFORE the
+ * 64^-0.25 scaling -- of the listed heads to q_tape, rows n_past .. n_past + n_new.  Logits and cache append are bit-identical
+ * to wm_decoder_step with not_alone = 1.                                                                                     */
+typedef struct wm_tap_io {
+    void* q_tape;            /* fp16 [batch][n_heads][capacity][64]: slot k of dim 1 belongs to heads[k] */
+    int32_t capacity;        /* rows per (utterance, head), >= n_past + n_new */
+    const int32_t* heads;    /* HOST array: layer * n_text_head + head, strictly ascending */
+    int32_t n_heads;
+} wm_tap_io;
+int wm_decoder_step_tap(const wm_engine* e, const wm_decoder_io* io, const wm_tap_io* tap, wm_stream_t stream);
+/* The alignment matrix and its DTW path for every utterance of a batch.  Per utterance b with N_all = n_tokens[b] forced
+ * tokens and F = n_frames[b] valid frames, per listed head: S[i][f] = q16[i] . k16[f] in fp32 (q16 = r16(tape * 64^-0.25),
+ * k16 = r16(K * 64^-0.25)), W = softmax over f < F, Z = (W - mean_i W) / std_i W (population std over the N_all rows; Z = 0
+ * where std == 0), median of filter_width along f with reflection at 0 and F - 1 (no filter when F <= filter_width / 2);
+ * Mtx = mean over the heads, added in the order of `heads`.  Rows n_prefix .. N_all - 2 of Mtx (N = N_all - n_prefix - 1 of
+ * them) are row 0 .. N - 1 of `matrix`, and wm_dtw's walk over -Mtx gives the path.  Utterances with N < 1 or F < 1 get
+ * path_len 0.  Nothing beyond row N - 1, column F - 1 of `matrix` and entry path_len - 1 of the paths is written.
+ * fp16 cross K/V only: an `engine` with WM_FLAG_INT8_CROSS_KV is refused (rc 1).                                             */
+typedef struct wm_align_io {
+    const wm_engine* engine;          /* optional: the decoder engine the tape came from (its flags and dims are checked) */
+    int32_t batch, n_text_head, n_audio_ctx;
+    const void* q_tape; int32_t capacity;      /* as wm_tap_io */
+    const void* const* cross; int32_t n_layers; /* HOST array of per-layer device pointers, fp16 [batch, 2, n_text_head, n_audio_ctx, 64] (layers without a listed head are not read) */
+    const int32_t* heads; int32_t n_heads;     /* HOST array, as wm_tap_io */
+    const int32_t* n_tokens;                   /* device int32 [batch]: N_all, clipped to cap_tokens */
+    const int32_t* n_frames;                   /* device int32 [batch]: F, clipped to n_audio_ctx */
+    int32_t n_prefix, filter_width;            /* filter_width odd, 1 .. 15 (1: no filter) */
+    int32_t cap_tokens;                        /* >= every n_tokens[b], <= capacity, <= 448 */
+    float* matrix; int32_t ld;                 /* optional fp32 [batch][cap_tokens][ld], ld >= n_audio_ctx (NULL: kept in the workspace) */
+    int32_t* path_text; int32_t* path_time;    /* int32 [batch][cap_tokens + n_audio_ctx] */
+    int32_t* path_len;                         /* int32 [batch] */
+    void* workspace; size_t workspace_bytes;   /* >= wm_align_workspace_bytes(batch, n_heads, cap_tokens, n_audio_ctx) */
+} wm_align_io;
+size_t wm_align_workspace_bytes(int batch, int n_heads, int cap_tokens, int n_audio_ctx);
+int wm_align(const wm_align_io* io, wm_stream_t stream);
+/* The DTW stage alone (test entry): utterance b walks x_b = x + b * x_bstride, fp32 [n_rows[b]][ldx] with n_cols[b] valid
+ * columns (device int32 arrays; values clipped to max_rows <= 1023 / max_cols).  cost[0][0] = 0, borders +inf,
+ * cost[i][j] = fp32(x[i-1][j-1] + min(c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1])) with the predecessor chosen by
+ * "c0 < c1 and c0 < c2: diagonal; else c1 < c0 and c1 < c2: up; else left"; the walk back from (n_rows, n_cols) is reversed
+ * into path_text / path_time [batch][path_ld], path_len[b] entries (0 when n_rows[b] < 1 or n_cols[b] < 1).               */
+size_t wm_dtw_workspace_bytes(int batch, int max_rows, int max_cols);
+int wm_dtw(const float* x, int ldx, int64_t x_bstride, int batch, const int32_t* n_rows, const int32_t* n_cols, int max_rows,
+           int max_cols, int32_t* path_text, int32_t* path_time, int path_ld, int32_t* path_len, void* workspace,
+           size_t workspace_bytes, wm_stream_t stream);
+
 /* ---- kernel-level entry points (parity tests, micro-benchmarks, roofline measurement) -----------*/
 /* C[M,N] = act(A[M,K] x W[N,K]^T * scale + bias) (+ residual); W fp16 or int8 (w8) row-major [N][K].
  * act: 0 none, 1 erf-GELU, 2 tanh-GELU.  Replaces CutlassFpAIntBGemmRunner::gemm /
