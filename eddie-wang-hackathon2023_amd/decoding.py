@@ -92,7 +92,8 @@ class MaximumLikelihoodRanker:
             scores = []
             for t, lp in zip(group, lps):
                 n = len(t)
-                penalty = n if self.length_penalty is None else ((5 + n) / 6) ** self.length_penalty
+                # (n = 0: a row closed before its first token, row_limit = 0 -- the empty rows of a long-form round; its sum is 0)
+                penalty = max(n, 1) if self.length_penalty is None else ((5 + n) / 6) ** self.length_penalty
                 scores.append(lp / penalty)
             picks.append(int(np.argmax(scores)))
         return picks
@@ -725,6 +726,19 @@ class WhisperDecoding:
         self.kv_cache, self.hooks = {}, []
         return languages, language_probs
 
+    def set_language_tokens(self, language_tokens: Sequence[int]) -> None:
+        """Hand in the language token of every row of the next main_loop call instead of running detect_language: for rows whose
+        language is known already (the later windows of a file, transcribe.py).  Same effect on the start sequences as the
+        language pass has: one row of initial tokens per utterance with its language token behind <|startoftranscript|>."""
+        if not self.is_multilingual:
+            raise ValueError("set_language_tokens: an English-only vocabulary has no language tokens")
+        valid = set(self.tokenizer.all_language_tokens)
+        language_tokens = [int(t) for t in language_tokens]
+        if not language_tokens or any(t not in valid for t in language_tokens):
+            raise ValueError("set_language_tokens: need one language token of the vocabulary per row")
+        self.tokens = torch.tensor([self.initial_tokens]).repeat(len(language_tokens), 1)
+        self.tokens[:, self.sot_index + 1] = torch.tensor(language_tokens, dtype=self.tokens.dtype)
+
     # ---- decoding loops ---------------------------------------------------------------------------------
     def _initial_token_rows(self, n_audio, device):
         tokens = self.tokens
@@ -1009,7 +1023,7 @@ class WhisperDecoding:
         live[1:] = torch.arange(hi - lo, dtype=torch.int32, device=live.device)
         return live
 
-    def _greedy(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None):
+    def _greedy(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None, temperature=None):
         """Fused logit rules + arg-max + append for utterances [lo, hi) of the batch state `st`."""
         tk = self.tokenizer
         io = native.WmGreedyIO()
@@ -1030,7 +1044,8 @@ class WhisperDecoding:
         io.row_limit = st['row_limit'][lo:hi].data_ptr()
         # temperature > 0: the draw happens in the same kernel (Gumbel-max, counter-based generator keyed on the global row: lo + b);
         # the seed lives in device memory so that a replayed graph draws afresh in every main_loop call
-        io.temperature, io.row0, io.seed_dev = float(self.options.temperature), lo, st['seed'].data_ptr()
+        io.temperature = float(self.options.temperature if temperature is None else temperature)     # (a per-call temperature: main_loop)
+        io.row0, io.seed_dev = lo, st['seed'].data_ptr()
         native.check(native.load_library().wm_greedy_step(C.byref(io), stream), "wm_greedy_step")
 
     def _beam(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, kv_table, ignore_eot, n_past_dev=None):
@@ -1064,21 +1079,26 @@ class WhisperDecoding:
                                        1 if self.use_int8_kv_cache else 2, st['parent'][lo:hi].data_ptr(), st['done'][lo:hi].data_ptr(),
                                        cur_len - 1, io.n_past_dev, stream), "wm_kv_reorder")
 
-    def main_loop(self, audio_features, ignore_eot: bool = False, row_limit=None, _retry: bool = False):
+    def main_loop(self, audio_features, ignore_eot: bool = False, row_limit=None, _retry: bool = False,
+                  temperature: Optional[float] = None):
         """`_main_loop` with the in-flight mark around it: word_timestamps reuses the loop's buffers and refuses to run inside it
         (a callback, another thread); the mark is cleared however the loop ends."""
         self._decode_in_flight += 1
         try:
-            return self._main_loop(audio_features, ignore_eot=ignore_eot, row_limit=row_limit, _retry=_retry)
+            return self._main_loop(audio_features, ignore_eot=ignore_eot, row_limit=row_limit, _retry=_retry, temperature=temperature)
         finally:
             self._decode_in_flight -= 1
 
-    def _main_loop(self, audio_features, ignore_eot: bool = False, row_limit=None, _retry: bool = False):
+    def _main_loop(self, audio_features, ignore_eot: bool = False, row_limit=None, _retry: bool = False,
+                   temperature: Optional[float] = None):
         """Greedy decoding, fast path.  Same return values as the reference's main_loop
         (tokens int64 [n, <=n_text_ctx+1], sum_logprobs fp32 [n], no_speech_probs list).
         `ignore_eot` (benchmarks with random weights) decodes `sample_len` tokens regardless.
         `row_limit` (optional, int [n]): a per-utterance `sample_len` -- row b ends with EOT after row_limit[b] sampled
         tokens (e.g. a bound from the clip's duration; bench.py's length distributions).
+        `temperature` (optional): this call's sampling temperature instead of the options' (the fallback ladder of long-form
+        transcription, transcribe.py).  The captured graphs bake the scalar in, so a call at another temperature has graphs of
+        its own; beam search and best_of keep the instance's temperature.
 
         Utterances are independent, so the batch is cut into `micro_batches` groups that advance in
         lock-step on separate HIP streams: while one group streams its cross-attention K/V (the
@@ -1086,7 +1106,13 @@ class WhisperDecoding:
         Rows that have emitted EOT drop out of the attention kernels and a group whose rows are all
         finished is no longer stepped (`skip_finished_rows`): the loop's cost follows the live rows."""
         features_in = audio_features
-        if self.options.temperature != 0 or self.n_group != 1 or self.beam:
+        temp = float(self.options.temperature if temperature is None else temperature)
+        if temp != self.options.temperature:
+            if self.beam or self.n_group != 1:
+                raise ValueError("a per-call temperature is not supported with beam_size / best_of: they decode at the instance's temperature")
+            if not self.device_sampling or not audio_features.is_cuda:
+                raise ValueError("a per-call temperature needs the device loop (device_sampling on, features on the GPU)")
+        if temp != 0 or self.n_group != 1 or self.beam:
             # Sampling options (W/decoding.py:274-300 temperature, :92-115 best_of + ranker).  Round 4: the device loop takes them --
             # the draw is a Gumbel-max inside the greedy kernel, candidates are rows like any others.  `device_sampling = False`
             # (or tensors that are not on the GPU) keeps the literal host loop: torch's generator, the draws the goldens hold.
@@ -1105,7 +1131,7 @@ class WhisperDecoding:
         one_row = (n_micro_ == 1 or self.groups_sequential) and not self.force_not_alone and any(hi - lo <= 8 for lo, hi in bounds_)
         if one_row and not _retry and native.chain_status()["error_pending"]:   # (a peek at a host word: no synchronisation)
             self._chain_gave_up("found before the decode loop", foreign=True)   # somebody else's give-up: said loudly, acknowledged, not ours to repeat
-        if self.options.temperature != 0:     # a fresh seed per call from torch's generator: torch.manual_seed makes a run repeatable
+        if temp != 0:     # a fresh seed per call from torch's generator: torch.manual_seed makes a run repeatable
             if not _retry:
                 st['seed'].copy_(torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32))
         cross = self._cross_persistent(audio_features, st)
@@ -1126,7 +1152,7 @@ class WhisperDecoding:
         n_micro, bounds = self._groups(n_batch)
         if self.cu_partition and n_micro > 1 and self.beam:
             raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
-        if self.cu_partition and n_micro > 1 and self.decoder_session.qkv_amax is None and row_limit is None:
+        if self.cu_partition and n_micro > 1 and self.decoder_session.qkv_amax is None and row_limit is None and temp == self.options.temperature:
             return self._main_loop_partitioned(audio_features, st, cross, L0, n_micro, bounds, ignore_eot)
         use_live = bool(self.skip_finished_rows) and not ignore_eot and max(hi - lo for lo, hi in bounds) <= 1024
         main = torch.cuda.current_stream()
@@ -1166,9 +1192,11 @@ class WhisperDecoding:
             if self.beam:
                 self._beam(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, gr['kv_table'], ignore_eot, n_past_dev=n_past_dev)
             else:
-                self._greedy(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, n_past_dev=n_past_dev)
+                self._greedy(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, n_past_dev=n_past_dev, temperature=temp)
 
         bkey = ('beam', bool(ignore_eot)) if self.beam else ()         # (ignore_eot is an argument of the captured beam step)
+        if temp != self.options.temperature:
+            bkey += (('temperature', temp),)                           # (so is the temperature: a per-call one has graphs of its own)
         last_issued = None
         for i in range(self.sample_len):
             for gr in groups:
@@ -1275,7 +1303,7 @@ class WhisperDecoding:
             # one-row groups run the token step as ONE launch whose workgroups wait for each other with bounded spins; a wait that was
             # given up invalidates the step and every token after it.  The utterance is decoded again, in this process, on the
             # launch-per-kernel path (the library has taken the device off the one-launch forms; the captured graphs are gone).
-            return self.main_loop(features_in, ignore_eot=ignore_eot, row_limit=row_limit, _retry=True)
+            return self.main_loop(features_in, ignore_eot=ignore_eot, row_limit=row_limit, _retry=True, temperature=temperature)
         return out
 
     def _main_loop_partitioned(self, audio_features, st, cross, L0, n_micro, bounds, ignore_eot):
@@ -1543,8 +1571,9 @@ class WhisperDecoding:
         text_bytes = text.encode("utf-8")
         return len(text_bytes) / len(zlib.compress(text_bytes))
 
-    def post_process(self, tokens, sum_logprobs, no_speech_probs, audio_features, languages):
-        """Slice, rank, detokenise (W/decoding.py:827-878); n_audio comes from the batch, not the config."""
+    def post_process(self, tokens, sum_logprobs, no_speech_probs, audio_features, languages, temperature: Optional[float] = None):
+        """Slice, rank, detokenise (W/decoding.py:827-878); n_audio comes from the batch, not the config.  `temperature`: what
+        the results say they were decoded at (main_loop's per-call temperature; default: the options')."""
         if audio_features.shape[0] == len(no_speech_probs):          # already one row per candidate (the reference's convention)
             audio_features = audio_features[:: self.n_group]
         no_speech_probs = no_speech_probs[:: self.n_group]
@@ -1565,7 +1594,7 @@ class WhisperDecoding:
             raise RuntimeError(f"inconsistent result lengths: {list(map(len, fields))}")
         return [
             DecodingResult(audio_features=features, language=language, tokens=toks, text=text, avg_logprob=avg,
-                           no_speech_prob=nsp, temperature=self.options.temperature,
+                           no_speech_prob=nsp, temperature=self.options.temperature if temperature is None else float(temperature),
                            compression_ratio=self.compression_ratio(text))
             for text, language, toks, features, avg, nsp in zip(*fields)
         ]

@@ -1,0 +1,236 @@
+"""Long-form transcription: the host statement of the contract.
+
+Upstream Whisper's `transcribe()`, restated: a window of 30 seconds moves over the audio; where it goes next is read off the
+timestamp tokens the decoder predicted (`cut_segments`), and a window whose text looks degenerate is decoded again at the next
+temperature of a ladder (`needs_fallback`).  `transcribe_reference` is that loop for one file, literally; `transcribe_batched`
+is the schedule the engine runs -- sequential per file, batched across files: every round decodes the current window of every
+unfinished file -- and must give every file the segments of the literal loop.
+
+Nothing here touches the device: the decoder is a callable handed in, so the rules and the scheduler are tested on the CPU
+with scripted decoders (tests/test_longform_cpu.py).  A decoder's result is anything with the fields of `DecodingResult`
+that the rules read: tokens, avg_logprob, no_speech_prob, compression_ratio, temperature.
+
+Units: everything is in mel frames.  W = 2 * n_audio_ctx frames per window (3000), fs = CHUNK_LENGTH / W seconds per frame;
+the timestamp token tb + k means k * 2 * fs seconds, 2 * k frames.
+
+One deliberate difference from upstream: an advance that is <= 0 or > segment_size becomes segment_size.  Upstream stands still
+for ever on <|0.00|><|0.00|>, and with random weights the timestamp indices run past the window.
+"""
+from __future__ import annotations
+
+from collections import deque
+from dataclasses import dataclass, field
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+CHUNK_LENGTH = 30
+TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)
+
+
+@dataclass
+class WindowResult:
+    """What the rules read of a decoded window (DecodingResult has the same fields)."""
+    tokens: List[int] = field(default_factory=list)
+    avg_logprob: float = 0.0
+    no_speech_prob: float = 0.0
+    compression_ratio: float = 1.0
+    temperature: float = 0.0
+
+
+@dataclass(frozen=True)
+class Thresholds:
+    compression_ratio_threshold: Optional[float] = 2.4
+    logprob_threshold: Optional[float] = -1.0
+    no_speech_threshold: Optional[float] = 0.6
+
+
+def _default_text(tokens: Sequence[int]) -> str:
+    return " ".join(str(t) for t in tokens)
+
+
+def _timestamp_pairs(tokens: Sequence[int], tb: int) -> Tuple[bool, List[int]]:
+    """(single_end, consecutive): whether the last two tokens are (text, timestamp), and the indices i with tokens[i - 1] and
+    tokens[i] both timestamps."""
+    ts = [t >= tb for t in tokens]
+    return ts[-2:] == [False, True], [i for i in range(1, len(tokens)) if ts[i - 1] and ts[i]]
+
+
+def predicted_advance(tokens: Sequence[int], tb: int, segment_size: int) -> int:
+    """Upstream's seek rule as it stands, BEFORE the guard: the frames of the last timestamp pair, or the whole window when
+    there is no pair or the window ends on a single timestamp."""
+    single_end, consecutive = _timestamp_pairs(tokens, tb)
+    if not consecutive or single_end:
+        return segment_size
+    return 2 * (int(tokens[consecutive[-1] - 1]) - tb)
+
+
+def cut_segments(tokens: Sequence[int], tb: int, seek: int, segment_size: int, fs: float,
+                 decode_text: Optional[Callable[[List[int]], str]] = None) -> Tuple[List[dict], int]:
+    """The segments of one window and how far the window moves: (segments, advance in frames).
+
+    `tokens`: the sampled tokens of the window (no start sequence, cut before EOT); `tb`: the first timestamp token; `seek`:
+    the window's first frame; `segment_size`: its frames of real audio.  A segment is {seek, start, end, text, tokens}, times in
+    seconds; its text is `decode_text` of its tokens below `tb`.  A segment whose start equals its end, or whose text is blank,
+    keeps its place with text = "" and tokens = []."""
+    decode_text = decode_text or _default_text
+    tokens = [int(t) for t in tokens]
+    single_end, consecutive = _timestamp_pairs(tokens, tb)
+    t0 = seek * fs
+    pieces = []                                        # (start, end, tokens)
+    if consecutive:
+        slices = consecutive + ([len(tokens)] if single_end else [])
+        last = 0
+        for cur in slices:
+            sl = tokens[last:cur]
+            pieces.append((t0 + (sl[0] - tb) * 2 * fs, t0 + (sl[-1] - tb) * 2 * fs, sl))
+            last = cur
+        # (what follows the last slice is dropped)
+    else:
+        duration = segment_size * fs
+        stamps = [t for t in tokens if t >= tb]
+        if stamps and stamps[-1] != tb:
+            duration = (stamps[-1] - tb) * 2 * fs
+        pieces.append((t0, t0 + duration, tokens))
+    advance = predicted_advance(tokens, tb, segment_size)
+    if advance <= 0 or advance > segment_size:         # the guard (module docstring)
+        advance = segment_size
+    segments = []
+    for start, end, sl in pieces:
+        text = decode_text([t for t in sl if t < tb])
+        if start == end or text.strip() == "":
+            text, sl = "", []
+        segments.append(dict(seek=seek, start=start, end=end, text=text, tokens=list(sl)))
+    return segments, advance
+
+
+def is_silence(result, logprob_threshold: Optional[float], no_speech_threshold: Optional[float]) -> bool:
+    return (no_speech_threshold is not None and logprob_threshold is not None
+            and result.no_speech_prob > no_speech_threshold and result.avg_logprob < logprob_threshold)
+
+
+def needs_fallback(result, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                   no_speech_threshold: Optional[float] = 0.6) -> bool:
+    """Decode the window again at the next temperature?  Too repetitive (compression ratio above its threshold) or too
+    unlikely (average log-probability below its threshold), each only when its threshold is given -- and never when the window
+    is silence (`is_silence`)."""
+    again = False
+    if compression_ratio_threshold is not None and result.compression_ratio > compression_ratio_threshold:
+        again = True
+    if logprob_threshold is not None and result.avg_logprob < logprob_threshold:
+        again = True
+    if is_silence(result, logprob_threshold, no_speech_threshold):
+        again = False
+    return again
+
+
+def skip_window(result, logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6) -> bool:
+    """No segment for this window?  The no-speech probability is above its threshold, unless the text is likely enough anyway
+    (logprob_threshold given and the average log-probability above it)."""
+    if no_speech_threshold is None or not result.no_speech_prob > no_speech_threshold:
+        return False
+    if logprob_threshold is not None and result.avg_logprob > logprob_threshold:
+        return False
+    return True
+
+
+def settle_window(result, tb: int, seek: int, segment_size: int, fs: float, th: Thresholds,
+                  decode_text: Optional[Callable[[List[int]], str]] = None) -> Tuple[List[dict], int]:
+    """The segments and the advance of a window whose result stands: skip, or cut; every segment carries the result's figures."""
+    if skip_window(result, th.logprob_threshold, th.no_speech_threshold):
+        return [], segment_size
+    segments, advance = cut_segments(result.tokens, tb, seek, segment_size, fs, decode_text)
+    for s in segments:
+        s.update(temperature=float(result.temperature), avg_logprob=float(result.avg_logprob),
+                 compression_ratio=float(result.compression_ratio), no_speech_prob=float(result.no_speech_prob))
+    return segments, advance
+
+
+def _thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold) -> Thresholds:
+    return Thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold)
+
+
+def _check_ladder(temperatures: Sequence[float]) -> Tuple[float, ...]:
+    temperatures = tuple(float(t) for t in temperatures)
+    if not temperatures or len(set(temperatures)) != len(temperatures):
+        raise ValueError(f"temperatures {temperatures}: need at least one, each once")
+    return temperatures
+
+
+def transcribe_reference(decode_one: Callable[[int, float], object], content_frames: int, *, window: int, timestamp_begin: int,
+                         temperatures: Sequence[float] = TEMPERATURES, compression_ratio_threshold: Optional[float] = 2.4,
+                         logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
+                         decode_text: Optional[Callable[[List[int]], str]] = None) -> List[dict]:
+    """The literal loop for one file of `content_frames` frames: `decode_one(seek, temperature)` decodes the window at `seek`."""
+    temperatures = _check_ladder(temperatures)
+    th = _thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold)
+    fs = CHUNK_LENGTH / window
+    segments: List[dict] = []
+    seek = 0
+    while seek < content_frames:
+        segment_size = min(window, content_frames - seek)
+        result = None
+        for t in temperatures:                         # the ladder: the first result that passes stands, else the last
+            result = decode_one(seek, t)
+            if not needs_fallback(result, *_astuple(th)):
+                break
+        cut, advance = settle_window(result, timestamp_begin, seek, segment_size, fs, th, decode_text)
+        segments += cut
+        seek += advance
+    return segments
+
+
+def _astuple(th: Thresholds):
+    return th.compression_ratio_threshold, th.logprob_threshold, th.no_speech_threshold
+
+
+def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], float, List[bool]], Sequence[object]],
+                       content_frames_list: Sequence[int], n_rows: int, *, window: int, timestamp_begin: int,
+                       temperatures: Sequence[float] = TEMPERATURES, compression_ratio_threshold: Optional[float] = 2.4,
+                       logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
+                       decode_text: Optional[Callable[[List[int]], str]] = None) -> List[List[dict]]:
+    """The scheduler: up to `n_rows` files are active, one row each; every round decodes the current window of each.
+
+    `decode_call(rows, temperature, live)`: rows[i] = (file, seek) of row i or None for an empty row, always n_rows of them;
+    live[i]: whether row i's result is wanted; returns n_rows results (anything for a row that is not live).  Per round one call
+    at temperatures[0] with every occupied row live, then, for each further temperature while any row still needs it, one call
+    in which only those rows are live (the rows are the round's: same files, same seeks).  A call carries one temperature, and
+    no (file, seek, temperature) is asked twice.  A finished file's row goes to the next waiting file from the following round
+    on; files without content never take a row.  Per file the segments equal `transcribe_reference`'s for the same decoder."""
+    temperatures = _check_ladder(temperatures)
+    if n_rows < 1:
+        raise ValueError(f"n_rows = {n_rows}: need at least one row")
+    th = _thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold)
+    fs = CHUNK_LENGTH / window
+    content = [int(c) for c in content_frames_list]
+    segments: List[List[dict]] = [[] for _ in content]
+    waiting = deque(f for f, c in enumerate(content) if c > 0)
+    rows: List[Optional[int]] = [None] * n_rows        # the file of every row
+    seek: Dict[int, int] = {}
+    while True:
+        for i in range(n_rows):
+            if rows[i] is None and waiting:
+                rows[i] = waiting.popleft()
+                seek[rows[i]] = 0
+        if all(f is None for f in rows):
+            break
+        asked = [None if f is None else (f, seek[f]) for f in rows]
+        live = [f is not None for f in rows]
+        final = list(decode_call(list(asked), temperatures[0], list(live)))
+        need = [live[i] and needs_fallback(final[i], *_astuple(th)) for i in range(n_rows)]
+        for t in temperatures[1:]:
+            if not any(need):
+                break
+            again = decode_call(list(asked), t, list(need))
+            for i in range(n_rows):
+                if need[i]:
+                    final[i] = again[i]
+                    need[i] = needs_fallback(again[i], *_astuple(th))
+        for i, f in enumerate(rows):
+            if f is None:
+                continue
+            segment_size = min(window, content[f] - seek[f])
+            cut, advance = settle_window(final[i], timestamp_begin, seek[f], segment_size, fs, th, decode_text)
+            segments[f] += cut
+            seek[f] += advance
+            if seek[f] >= content[f]:
+                rows[i] = None
+    return segments

@@ -1,0 +1,230 @@
+"""transcribe.py: long-form transcription -- files of any length, several at a time.
+
+Upstream Whisper's `transcribe()` over the engines: a 30-second window moves over each file, seeking by the timestamp tokens
+the decoder predicted, and a window whose text looks degenerate is decoded again at the next temperature of a ladder.
+longform.py states the contract (the rules and the schedule, on the host, tested on the CPU); this module is the device side of
+`longform.transcribe_batched`'s `decode_call`:
+
+  * one file is strictly sequential, the engines' strength is the batch: every round decodes the CURRENT window of every
+    unfinished file, one file per row;
+  * the round's windows are cut on the device in one launch (wm_mel_windows, csrc/windows.hip) from the files' log-mels, each
+    at its own position and of its own length;
+  * the encoder runs once per round; a fallback call hands main_loop the SAME features tensor, so the cross K/V stay in place;
+  * every decoder call has the same number of rows: rows that are empty or already settled get row_limit = 0 -- the greedy
+    kernel closes them with EOT at the first step and the attention kernels drop them -- because a change of batch size makes
+    WhisperDecoding free and re-allocate its whole buffer set and its graphs;
+  * a file's language is detected on its first window (unless the options name one) and kept for all of its windows.
+
+Refused in this version (ValueError): an instance built with `prompt` / `prefix`, `condition_on_previous_text` (the rows of a
+batch share one start length), and beam_size / best_of together with a ladder of more than one temperature.  Out of scope: word
+timestamps per segment, clip_timestamps, the hallucination-silence heuristics, resampling.
+
+CLI: python transcribe.py --engine_dir eng --input_file a.flac [b.flac ...] --vocab multilingual.tiktoken [--temperature T ...]
+[--no_fallback] prints one "[mm:ss.mmm --> mm:ss.mmm] text" line per non-empty segment.
+"""
+from __future__ import annotations
+
+import argparse
+import logging
+from pathlib import Path
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+import longform
+import native
+from decoding import DecodingOptions, WhisperDecoding
+from encoding import WhisperEncoding
+from tokenizer import Tokenizer
+
+
+def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], condition_on_previous_text: bool = False) -> None:
+    """The combinations this version refuses (module docstring)."""
+    opt = decoding.options
+    if opt.prompt or opt.prefix:
+        raise ValueError("transcribe: an instance built with prompt / prefix is not supported in this version")
+    if condition_on_previous_text:
+        raise ValueError("transcribe: condition_on_previous_text is not supported in this version "
+                         "(the rows of a batch share one start length)")
+    if decoding.beam or decoding.n_group != 1:
+        if len(temperatures) != 1 or float(temperatures[0]) != float(opt.temperature):
+            raise ValueError("transcribe: beam_size / best_of decode at the instance's temperature: give that one temperature "
+                             f"({opt.temperature}; no fallback), not the ladder {tuple(temperatures)}")
+
+
+def mel_windows(mels: Sequence[Optional[torch.Tensor]], seeks: Sequence[int], n_mels: int, n_window: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp16 [len(mels), n_mels, n_window]: row b is mels[b][:, seeks[b] : seeks[b] + n_window], zero behind the mel's end and
+    all zero for a None entry (wm_mel_windows: one launch for the ragged batch, on the current stream)."""
+    n = len(mels)
+    assert n >= 1 and len(seeks) == n
+    dev = next((m.device for m in mels if m is not None), out.device if out is not None else torch.device("cuda"))
+    for m in mels:
+        assert m is None or (m.is_cuda and m.dtype == torch.float16 and m.dim() == 2 and m.shape[0] == n_mels and m.is_contiguous()), \
+            "a mel must be a contiguous fp16 [n_mels, frames] tensor on the GPU"
+    table = torch.tensor([[0 if m is None else m.data_ptr() for m in mels],
+                          [0 if m is None else m.shape[1] for m in mels],
+                          [int(s) for s in seeks]], dtype=torch.int64).to(dev, non_blocking=False)
+    frames, seek = table[1].to(torch.int32), table[2].to(torch.int32)
+    if out is None:
+        out = torch.empty((n, n_mels, n_window), dtype=torch.float16, device=dev)
+    assert out.shape == (n, n_mels, n_window) and out.dtype == torch.float16 and out.is_contiguous()
+    native.check(native.load_library().wm_mel_windows(table[0].data_ptr(), frames.data_ptr(), seek.data_ptr(), n, n_mels, n_window,
+                                                      out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "wm_mel_windows")
+    return out
+
+
+def default_rows(decoding: WhisperDecoding, n_files: int, device) -> int:
+    """min(files, what fits): the decoder state of a row (state_bytes_per_utterance) against four fifths of the free memory."""
+    free, _ = torch.cuda.mem_get_info(device)
+    per_row = decoding.state_bytes_per_utterance() * decoding.n_group
+    return max(1, min(n_files, int(0.8 * free // per_row)))
+
+
+def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: Sequence[torch.Tensor],
+                   content_frames: Sequence[int], *, temperatures: Sequence[float] = longform.TEMPERATURES,
+                   compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                   no_speech_threshold: Optional[float] = 0.6, n_rows: Optional[int] = None, trace: Optional[list] = None,
+                   condition_on_previous_text: bool = False) -> List[dict]:
+    """Transcribe files given as log-mels: mels[f] fp16 [n_mels, content_frames[f] + W] on the GPU (W = 2 * n_audio_ctx; the last
+    W frames are the log-mel of 30 s of padding: whisper_utils.long_log_mel_device).  One dict per file: language, text, segments;
+    a segment: seek, start, end (seconds), text, tokens, temperature, avg_logprob, compression_ratio, no_speech_prob.
+    `n_rows`: rows of every decoder call (default: min(files, what fits)).  `trace`: a list that receives one dict per decoder
+    call (rows, live, temperature, windows, results, ...: tests, diagnostics)."""
+    temperatures = tuple(float(t) for t in (temperatures if isinstance(temperatures, (tuple, list)) else [temperatures]))
+    check_supported(decoding, temperatures, condition_on_previous_text)
+    n_files = len(mels)
+    if len(content_frames) != n_files:
+        raise ValueError(f"transcribe: {len(content_frames)} content_frames for {n_files} mels")
+    cfg = decoding.decoder_config
+    W = 2 * cfg['num_audio_ctx']
+    tk = decoding.tokenizer
+    if n_files == 0:
+        return []
+    n_mels = int(mels[0].shape[0])
+    for f, (m, c) in enumerate(zip(mels, content_frames)):
+        if m.dim() != 2 or m.shape[0] != n_mels or m.shape[1] < c or c < 0:
+            raise ValueError(f"transcribe: mel {f} has shape {tuple(m.shape)} for {c} frames of content")
+    dev = mels[0].device
+    mels = [m.to(torch.float16).contiguous() for m in mels]
+    if n_rows is None:
+        n_rows = default_rows(decoding, max(1, sum(1 for c in content_frames if c > 0)), dev)
+    n_group = decoding.n_group
+
+    # the language of every file: named by the options, or detected on the file's first window
+    multilingual = decoding.is_multilingual
+    named = None
+    if multilingual and decoding.options.language is not None:
+        named = Tokenizer._defaults(True, decoding.options.language, None)[0]
+    file_language: List[Optional[str]] = [named if multilingual else 'en'] * n_files
+    default_token = tk.special_tokens[f"<|{named or 'en'}|>"] if multilingual else None
+
+    win = torch.zeros((n_rows, n_mels, W), dtype=torch.float16, device=dev)
+    state = dict(rows=None, features=None, round=-1, languages=None, tokens=None, windows_host=None, detected={})
+
+    def begin_round(rows):
+        state['round'] += 1
+        state['rows'] = list(rows)
+        mel_windows([None if r is None else mels[r[0]] for r in rows], [0 if r is None else r[1] for r in rows], n_mels, W, out=win)
+        state['features'] = features = encoding.get_audio_features(win)
+        state['windows_host'] = win.cpu() if trace is not None else None
+        state['detected'] = {}
+        if multilingual:
+            fresh = [i for i, r in enumerate(rows) if r is not None and file_language[r[0]] is None]
+            if fresh:
+                langs, _ = decoding.detect_language(features)
+                for i in fresh:
+                    file_language[rows[i][0]] = langs[i]
+                    state['detected'][rows[i][0]] = (i, langs[i])
+            state['languages'] = [(named or 'en') if r is None else file_language[r[0]] for r in rows]
+            state['tokens'] = [default_token if r is None else tk.special_tokens[f"<|{file_language[r[0]]}|>"] for r in rows]
+        else:
+            state['languages'], state['tokens'] = ['en'] * len(rows), None
+
+    def decode_call(rows, temperature, live):
+        assert len(rows) == n_rows and len(live) == n_rows
+        new_round = state['rows'] != list(rows)
+        if new_round:
+            begin_round(rows)
+        features = state['features']
+        if state['tokens'] is not None:
+            decoding.set_language_tokens(state['tokens'])
+        limit = torch.tensor([(1 << 30) if on else 0 for on in live], dtype=torch.int32).repeat_interleave(n_group)
+        per_call = None if (decoding.beam or n_group != 1) else temperature
+        tokens, sum_logprobs, no_speech_probs = decoding.main_loop(features, row_limit=limit, temperature=per_call)
+        results = decoding.post_process(tokens, sum_logprobs, no_speech_probs, features, state['languages'], temperature=temperature)
+        results = [r if on else None for r, on in zip(results, live)]
+        if trace is not None:
+            st = next(iter(decoding._state.values()))
+            trace.append(dict(round=state['round'], new_round=new_round, temperature=temperature, rows=list(rows), live=list(live),
+                              row_limit=limit.clone(), windows=state['windows_host'], languages=list(state['languages']),
+                              language_tokens=None if state['tokens'] is None else list(state['tokens']),
+                              detected=dict(state['detected']) if new_round else {}, results=results,
+                              n_states=len(decoding._state), n_graphs=len(st['graphs'])))
+        return results
+
+    segments = longform.transcribe_batched(
+        decode_call, [int(c) for c in content_frames], n_rows, window=W, timestamp_begin=tk.timestamp_begin,
+        temperatures=temperatures, compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
+        no_speech_threshold=no_speech_threshold, decode_text=tk.decode)
+    out = []
+    for f in range(n_files):
+        text = tk.decode([t for s in segments[f] for t in s['tokens']]).strip()
+        out.append(dict(language=file_language[f], text=text, segments=segments[f]))
+    return out
+
+
+def transcribe(encoding: WhisperEncoding, decoding: WhisperDecoding, audio_or_paths, **kw) -> List[dict]:
+    """`transcribe_mel` over files (FLAC / 16 kHz PCM16 WAV paths) or waveforms (float arrays at 16 kHz): the log-mel of each
+    whole file comes from one wm_log_mel call (whisper_utils.long_log_mel_device)."""
+    import whisper_utils as wu
+    mels, content = [], []
+    for a in audio_or_paths:
+        if isinstance(a, (str, Path)):
+            a = wu.load_audio(str(a))
+        a = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a, dtype=np.float32))
+        mel, frames = wu.long_log_mel_device(a.float().flatten().cuda())
+        mels.append(mel)
+        content.append(frames)
+    return transcribe_mel(encoding, decoding, mels, content, **kw)
+
+
+def format_timestamp(seconds: float) -> str:
+    ms = round(seconds * 1000.0)
+    return f"{ms // 60000:02d}:{ms % 60000 // 1000:02d}.{ms % 1000:03d}"
+
+
+def parse_arguments(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--log_level', type=str, default='error')
+    parser.add_argument('--engine_dir', type=str, default='whisper_outputs')
+    parser.add_argument('--input_file', type=str, nargs='+', required=True, help='.flac / 16 kHz .wav files of any length')
+    parser.add_argument('--vocab', type=str, default=None, help='path to multilingual.tiktoken (text output)')
+    parser.add_argument('--language', type=str, default=None, help='language of the files (default: detected per file)')
+    parser.add_argument('--temperature', type=float, nargs='+', default=list(longform.TEMPERATURES),
+                        help='the fallback ladder (default: 0 0.2 0.4 0.6 0.8 1)')
+    parser.add_argument('--no_fallback', default=False, action='store_true', help='decode every window once, at the first temperature')
+    parser.add_argument('--rows', type=int, default=None, help='rows of a decoder call (default: min(files, what fits))')
+    return parser.parse_args(argv)
+
+
+def main(args) -> List[dict]:
+    logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.ERROR))
+    torch.cuda.set_device(0)
+    engine_dir = Path(args.engine_dir)
+    encoding = WhisperEncoding(engine_dir)
+    decoding = WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language))
+    temperatures = tuple(args.temperature[:1] if args.no_fallback else args.temperature)
+    results = transcribe(encoding, decoding, args.input_file, temperatures=temperatures, n_rows=args.rows)
+    for path, result in zip(args.input_file, results):
+        if len(results) > 1:
+            print(f"{path} ({result['language']})")
+        for s in result['segments']:
+            if s['text'].strip():
+                print(f"[{format_timestamp(s['start'])} --> {format_timestamp(s['end'])}] {s['text'].strip()}")
+    return results
+
+
+if __name__ == '__main__':
+    main(parse_arguments())

@@ -175,3 +175,17 @@ def log_mel_spectrogram_device(audio: torch.Tensor, n_mels: int = N_MELS, dtype:
     native.check(lib.wm_log_mel(a.data_ptr(), B, n, a.stride(0), filt.data_ptr(), n_mels, o16, o32, ws.data_ptr(),
                                 C.c_size_t(ws_bytes), s), "wm_log_mel")
     return out[0] if single else out
+
+
+def long_log_mel_device(audio: torch.Tensor, n_mels: int = N_MELS):
+    """The log-mel of a whole file for long-form transcription (transcribe.py): `audio` fp32 [n] on the GPU, any length ->
+    (mel fp16 [n_mels, content_frames + N_FRAMES], content_frames).  Upstream's `log_mel_spectrogram(audio, padding=N_SAMPLES)`
+    as ONE wm_log_mel call: N_SAMPLES zeros are appended (and zeros up to a whole hop, which the kernel asks for), the first
+    (n + N_SAMPLES) // HOP_LENGTH frames are kept -- the last N_FRAMES of them are the log-mel of the 30 s of padding -- and the
+    clamp to max - 8 is taken over the whole file, as upstream does."""
+    assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 1, "audio must be a 1-D fp32 tensor on the GPU"
+    n = int(audio.shape[0])
+    padded = -(-(n + N_SAMPLES) // HOP_LENGTH) * HOP_LENGTH
+    mel = log_mel_spectrogram_device(F.pad(audio, (0, padded - n)), n_mels=n_mels, dtype=torch.float16)
+    n_frames = (n + N_SAMPLES) // HOP_LENGTH
+    return mel[:, :n_frames].contiguous(), n_frames - N_FRAMES

@@ -388,6 +388,13 @@ int wm_embed(const int32_t* tokens, int tokens_ld, int M, int L, const void* emb
              void* x, int ldx, int n_vocab, const int32_t* t_dev, uint32_t* generation, wm_stream_t stream);
 /* mel fp16 [B][n_mels][T] -> out fp16 [B][T + 2][n_mels], rows 0 and T + 1 of every utterance zero. */
 int wm_mel_transpose_pad(const void* mel, int B, int n_mels, int T, void* out, wm_stream_t stream);
+/* The windows of a ragged batch of log-mels (long-form transcription: one file per row, each at its own position):
+ *   out[b][m][j] = seek[b] + j < src_frames[b] ? src[b][m * src_frames[b] + seek[b] + j] : 0,   out fp16 [batch][n_mels][n_window].
+ * src: DEVICE array of `batch` device pointers to fp16 [n_mels][src_frames[b]] (a null entry gives a zero row); src_frames, seek:
+ * DEVICE int32 arrays (seek >= 0; any parity).  Everything per row is read on the device: one launch, no host synchronisation,
+ * capturable.  Added under ABI 8 (an entry only; no struct changes). */
+int wm_mel_windows(const void* const* src, const int32_t* src_frames, const int32_t* seek, int batch, int n_mels, int n_window,
+                   void* out, wm_stream_t stream);
 /* zeroes rows 0 and Tpad - 1 of every utterance of buf fp16 [B][Tpad][C]. */
 int wm_zero_pad_rows(void* buf, int B, int Tpad, int C, wm_stream_t stream);
 /* ids[b] = arg-max of row b of fp16 logits (first index wins ties).  The decode loop itself uses
