@@ -91,7 +91,7 @@ __device__ __forceinline__ float wave_dpp(float v) {
 // inlined, MFMA kernels included -- 11 more idle cycles per reduction, nothing next to the memory round trips these kernels
 // are made of.  No kernel needs the guarded forms today: gemv_small / gemm_rows reduce in their LayerNorm prologues, before the
 // wave's first MFMA (wave_sum_pre_mfma), rowops, greedy and attn_decode have no MFMA at all (wave_sum_nomfma / wave_max_nomfma:
-// the same butterfly without the wait states); attn_encoder keeps __shfl_xor.  The guarded forms stay for any reduction that
+// the same butterfly without the wait states); attn_encoder leaves the moves to the compiler (lane_xor_step below).  The guarded forms stay for any reduction that
 // does follow an MFMA.
 #define WM_SWAP_GUARD "s_nop 7\n\ts_nop 7\n\ts_nop 2\n\t"
 __device__ __forceinline__ void wave_swap32(int& x, int& y) {
@@ -189,6 +189,56 @@ __device__ __forceinline__ float wave_max(float v) {
 // For data that no matrix instruction of the wave has in flight (freshly converted values in an epilogue).
 __device__ __forceinline__ void lane_rows_swap16(uint32_t& a, uint32_t& b) {
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
+}
+// One cross-row butterfly step (lane ^ 16 with v_permlane16_swap, lane ^ 32 with v_permlane32_swap) of N maxima or sums at once,
+// for a wave that HAS matrix instructions in flight (the encoder attention's softmax).  The copies b = a are plain C++: the
+// compiler emits the moves and its hazard recognizer puts the wait states a matrix instruction in flight asks for in front of
+// them, and only as many as the instructions in between leave open (the guarded wave_swap16 / 32 above always wait 19).  The assembly holds only the swaps, whose operands ordinary vector instructions wrote last, and one pair of wait
+// states for the lot.  After a swap a and b hold own and partner (even rows / lower half) or partner and own: max and + are
+// commutative, so every lane gets what __shfl_xor + max / + gives, bit for bit.
+#define WM_SWAP4(INS) "s_nop 1\n\t" INS " %0, %4\n\t" INS " %1, %5\n\t" INS " %2, %6\n\t" INS " %3, %7\n\ts_nop 1"
+#define WM_SWAP2(INS) "s_nop 1\n\t" INS " %0, %2\n\t" INS " %1, %3\n\ts_nop 1"
+#define WM_MAX4 "\n\tv_max_f32 %0, %0, %4\n\tv_max_f32 %1, %1, %5\n\tv_max_f32 %2, %2, %6\n\tv_max_f32 %3, %3, %7"
+#define WM_MAX2 "\n\tv_max_f32 %0, %0, %2\n\tv_max_f32 %1, %1, %3"
+#define WM_OPS4 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])
+#define WM_OPS2 : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1])
+// SUM: a[i] + b[i] is left to the caller's C++; maxima are taken inside the statement (a[i] = max(a[i], b[i])): on values that
+// come out of an assembly statement fmaxf() first quiets each operand (v_max_f32 x, x, x), three instructions per maximum
+// instead of one, in a loop that is bound by vector issue.  For finite values and infinities v_max_f32 IS fmaxf; with a NaN operand
+// both return the other operand, and they differ only in whether a signalling NaN comes out quieted (attn_encoder.hip: contract).
+// Wait states: LLVM's hazard recognizer for gfx950 (GCNHazardRecognizer, the v_permlane*_swap entries) asks for 2 wait states between
+// a VALU write of a register and a v_permlane*_swap that reads it, and for 2 between the swap and a VALU read of its results:
+// `s_nop 1` on either side, as in lane_rows_swap16 below.
+template <int N, bool ROWS16, bool SUM>
+__device__ __forceinline__ void lane_swap_pairs(uint32_t (&a)[N], uint32_t (&b)[N]) {
+    static_assert(N == 2 || N == 4, "lane_swap_pairs: 2 or 4 values");
+    if constexpr (N == 4) {
+        if constexpr (ROWS16 && SUM) asm volatile(WM_SWAP4("v_permlane16_swap_b32") WM_OPS4);
+        else if constexpr (ROWS16) asm volatile(WM_SWAP4("v_permlane16_swap_b32") WM_MAX4 WM_OPS4);
+        else if constexpr (SUM) asm volatile(WM_SWAP4("v_permlane32_swap_b32") WM_OPS4);
+        else asm volatile(WM_SWAP4("v_permlane32_swap_b32") WM_MAX4 WM_OPS4);
+    } else {
+        if constexpr (ROWS16 && SUM) asm volatile(WM_SWAP2("v_permlane16_swap_b32") WM_OPS2);
+        else if constexpr (ROWS16) asm volatile(WM_SWAP2("v_permlane16_swap_b32") WM_MAX2 WM_OPS2);
+        else if constexpr (SUM) asm volatile(WM_SWAP2("v_permlane32_swap_b32") WM_OPS2);
+        else asm volatile(WM_SWAP2("v_permlane32_swap_b32") WM_MAX2 WM_OPS2);
+    }
+}
+#undef WM_SWAP4
+#undef WM_SWAP2
+#undef WM_MAX4
+#undef WM_MAX2
+#undef WM_OPS4
+#undef WM_OPS2
+template <int N, bool ROWS16, bool SUM>
+__device__ __forceinline__ void lane_xor_step(float (&v)[N]) {
+    uint32_t a[N], b[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) a[i] = b[i] = __builtin_bit_cast(uint32_t, v[i]);
+    lane_swap_pairs<N, ROWS16, SUM>(a, b);
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        v[i] = SUM ? __builtin_bit_cast(float, a[i]) + __builtin_bit_cast(float, b[i]) : __builtin_bit_cast(float, a[i]);
 }
 __device__ __forceinline__ float r16(float x) { return (float)(h16)x; }   // round through fp16
 // The same rounding with the operand MATERIALISED as an fp32 value first.  Where the operand is a product, hipcc otherwise fuses

@@ -26,7 +26,7 @@ for persist in (0, 1):
     labels = {l.split(":")[0]: i for i, l in enumerate(body) if re.match(r"^\.LBB\d+_\d+:", l)}
     best = None
     for i, l in enumerate(body):
-        b = re.match(r"\s+s_cbranch_\w+ (\.LBB\d+_\d+)", l)
+        b = re.match(r"\s+s_c?branch(?:_\w+)? (\.LBB\d+_\d+)", l)       # (the back edge may be a plain s_branch behind the conditional exit)
         if b and b.group(1) in labels and labels[b.group(1)] < i:
             seg = body[labels[b.group(1)]:i + 1]
             n_mfma = sum("v_mfma" in x for x in seg)
