@@ -170,6 +170,9 @@ int launch_zero_pad_rows(h16* buf, int B, int Tpad, int C, hipStream_t stream);
 // windows.hip: out[b][m][j] = src[b][m][seek[b] + j], zero from src_frames[b] on (src / src_frames / seek: device arrays)
 int launch_mel_windows(const h16* const* src, const int32_t* src_frames, const int32_t* seek, int batch, int n_mels,
                        int n_window, h16* out /*[batch][n_mels][n_window]*/, hipStream_t stream);
+// resample.hip: interleaved PCM (dtype 0 f32, 1 i16, 2 i32) -> mono fp32 at L / M times the rate, table fp32 [2 half + 1][L]
+int launch_resample(const void* pcm, int dtype, int channels, long n_in, float scale, const float* table, int L, int M, int half,
+                    float* out, long n_out, hipStream_t stream);
 int launch_layernorm(const h16* x, int ldx, int M, int N, const h16* g, const h16* b, h16* out, int ldo,
                      hipStream_t stream);
 

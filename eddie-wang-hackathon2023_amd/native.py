@@ -82,7 +82,7 @@ EXPORTS = (
     "wm_beam_workspace_bytes", "wm_beam_step", "wm_kv_reorder",
     "wm_gemm_ex", "wm_row_finish", "wm_embed", "wm_mel_transpose_pad", "wm_zero_pad_rows",
     "wm_decoder_step_tap", "wm_align_workspace_bytes", "wm_align", "wm_dtw_workspace_bytes", "wm_dtw",
-    "wm_mel_windows",
+    "wm_mel_windows", "wm_resample",
 )
 
 
@@ -341,6 +341,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_mel_transpose_pad.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.wm_zero_pad_rows.argtypes = [vp, i32, i32, i32, vp]
     lib.wm_mel_windows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.wm_resample.argtypes = [vp, i32, i32, C.c_int64, C.c_float, vp, i32, i32, i32, vp, C.c_int64, vp]
     lib.wm_decoder_step_tap.argtypes = [vp, C.POINTER(WmDecoderIO), C.POINTER(WmTapIO), vp]
     lib.wm_align_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.wm_align_workspace_bytes.restype = sz

@@ -3,11 +3,12 @@ reference (W/run.py:21-63): prints "transcribe time <s>" and the text.
 
 Audio front-end: the reference shells out to ffmpeg and computes the log-mel on the GPU with
 torch.stft (W/whisper_utils.py:17-146).  ffmpeg is not on these boxes; `--input_file` accepts a
-`.flac` (decoded on the device: wm_flac_decode, csrc/flac_decode.hip -- LibriSpeech's format), a
-16 kHz mono `.wav` (PCM16, standard library), a `.npy` log-mel `[80, 3000]` or the keyword
-`synthetic`; the log-mel itself is the HIP front end (wm_log_mel, csrc/frontend.hip: STFT + mel +
+`.flac` (wm_flac_decode, csrc/flac_decode.hip -- LibriSpeech's format), a `.wav` (PCM 8 / 16 / 24 / 32
+bit or float32), a `.npy` log-mel `[80, 3000]` or the keyword `synthetic`; a file at another rate than
+16 kHz (4 kHz .. 192 kHz) or with several channels is downmixed and resampled on the device
+(wm_resample, csrc/resample.hip: ffmpeg's `-ar 16000 -ac 1`, with this project's own filter); the log-mel itself is the HIP front end (wm_log_mel, csrc/frontend.hip: STFT + mel +
 log on the device), held to the reference's golden mel in
-tests/test_gpu_model.py.  m4a / resampling (ffmpeg's job in the reference) stay out of scope.
+tests/test_gpu_model.py.  m4a and the other compressed formats (ffmpeg's job in the reference) stay out of scope.
 """
 from __future__ import annotations
 
@@ -27,7 +28,8 @@ def parse_arguments(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--log_level', type=str, default='error')
     parser.add_argument('--engine_dir', type=str, default='whisper_outputs')
-    parser.add_argument('--input_file', type=str, default='synthetic')
+    parser.add_argument('--input_file', type=str, default='synthetic',
+                        help="'synthetic', a .npy log-mel, or a .flac / .wav at any rate from 4 kHz to 192 kHz (resampled to 16 kHz mono)")
     parser.add_argument('--vocab', type=str, default=None, help='path to multilingual.tiktoken (text output)')
     parser.add_argument('--beam_size', type=int, default=None, help='beam search with that many beams (1..8; default: greedy)')
     parser.add_argument('--patience', type=float, default=None, help='beam search: finished candidates per utterance = beam_size * patience')

@@ -17,7 +17,8 @@ longform.py states the contract (the rules and the schedule, on the host, tested
 
 Refused in this version (ValueError): an instance built with `prompt` / `prefix`, `condition_on_previous_text` (the rows of a
 batch share one start length), and beam_size / best_of together with a ladder of more than one temperature.  Out of scope: word
-timestamps per segment, clip_timestamps, the hallucination-silence heuristics, resampling.
+timestamps per segment, clip_timestamps, the hallucination-silence heuristics.  Files at any rate from 4 kHz to 192 kHz and with
+several channels are downmixed and resampled to 16 kHz on the device (whisper_utils.load_audio_device, wm_resample).
 
 CLI: python transcribe.py --engine_dir eng --input_file a.flac [b.flac ...] --vocab multilingual.tiktoken [--temperature T ...]
 [--no_fallback] prints one "[mm:ss.mmm --> mm:ss.mmm] text" line per non-empty segment.
@@ -176,13 +177,14 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
 
 
 def transcribe(encoding: WhisperEncoding, decoding: WhisperDecoding, audio_or_paths, **kw) -> List[dict]:
-    """`transcribe_mel` over files (FLAC / 16 kHz PCM16 WAV paths) or waveforms (float arrays at 16 kHz): the log-mel of each
-    whole file comes from one wm_log_mel call (whisper_utils.long_log_mel_device)."""
+    """`transcribe_mel` over files (FLAC / WAV paths at any rate, any channel count: whisper_utils.load_audio_device resamples on
+    the GPU) or waveforms (float arrays or tensors at 16 kHz): the log-mel of each whole file comes from one wm_log_mel call
+    (whisper_utils.long_log_mel_device)."""
     import whisper_utils as wu
     mels, content = [], []
     for a in audio_or_paths:
         if isinstance(a, (str, Path)):
-            a = wu.load_audio(str(a))
+            a = wu.load_audio_device(str(a))
         a = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a, dtype=np.float32))
         mel, frames = wu.long_log_mel_device(a.float().flatten().cuda())
         mels.append(mel)
@@ -199,7 +201,7 @@ def parse_arguments(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--log_level', type=str, default='error')
     parser.add_argument('--engine_dir', type=str, default='whisper_outputs')
-    parser.add_argument('--input_file', type=str, nargs='+', required=True, help='.flac / 16 kHz .wav files of any length')
+    parser.add_argument('--input_file', type=str, nargs='+', required=True, help='.flac / .wav files of any length, 4 kHz .. 192 kHz, any channel count (resampled to 16 kHz mono on the GPU)')
     parser.add_argument('--vocab', type=str, default=None, help='path to multilingual.tiktoken (text output)')
     parser.add_argument('--language', type=str, default=None, help='language of the files (default: detected per file)')
     parser.add_argument('--temperature', type=float, nargs='+', default=list(longform.TEMPERATURES),

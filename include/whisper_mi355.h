@@ -552,6 +552,20 @@ int wm_log_mel(const float* audio, int batch, int n_samples, int64_t audio_ld, c
                int n_mels, void* mel_f16, float* mel_f32, void* workspace, size_t workspace_bytes,
                wm_stream_t stream);
 
+/* Resampler of the front end (the `-ar 16000 -ac 1` of the reference's ffmpeg call, W/whisper_utils.py:17-54): interleaved PCM
+ * pcm [n_in][channels] on the device (dtype 0: float32, 1: int16, 2: int32; 1..8 channels) -> out fp32 [n_out], mono, at L / M
+ * times the input rate, n_out = ceil(n_in L / M).  The downmix is fused into the staging of the input:
+ *   x[k] = (fp32(v[k][0]) + fp32(v[k][1]) + ...  in channel order, in fp32) / fp32(channels) * scale
+ * (scale: 2^-(bits - 1) for integer PCM, 1 for float), and with i = floor(n M / L), p = (n M) mod L, T = 2 half + 1
+ *   out[n] = sum_{j = 0 .. T - 1} H[p][j] * x[i - half + j]     fp32 FMAs in tap order, x zero outside [0, n_in):
+ * no delay, output n sits at input time n M / L; deterministic.  `table` is the DEVICE copy of H, transposed and ordered by
+ * r = n mod L:  table[j * L + r] = H[(r M) mod L][j], fp32 [T][L] (whisper_utils.resample_filter states H; resample_device builds
+ * this layout).  All arithmetic on n M is 64-bit.  rc 1 without a launch: a null pointer, channels outside 1..8, an unknown dtype,
+ * L == M, L / M / half < 1, n_in < 1, n_out != ceil(n_in L / M), or a ratio whose tile does not fit LDS (M / L above ~14).
+ * Added under ABI 8 (an entry only; no struct changes). */
+int wm_resample(const void* pcm, int dtype, int channels, int64_t n_in, float scale, const float* table, int L, int M, int half,
+                float* out, int64_t n_out, wm_stream_t stream);
+
 /* FLAC decoder (host code, no GPU needed): replaces the ffmpeg subprocess of load_audio
  * (W/whisper_utils.py:17-54) for the LibriSpeech .flac files.  wm_flac_decode writes interleaved
  * int32 samples [n][channels]; frame CRC-8 / CRC-16 are verified, `md5` is the STREAMINFO signature of
