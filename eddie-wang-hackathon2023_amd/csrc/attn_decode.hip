@@ -12,6 +12,15 @@
 //   current call are used un-quantised (attention.py:281-348; same contract as the MMHA kernel,
 //   decoderMaskedMultiheadAttentionTemplate.h:1501-1517, Utils.h:2276-2286,2357-2390).
 //
+//   Right-aligned rows (AttnSelfParams::row_start, the RS instantiations): utterance b's sequence begins at slot s = row_start[b]
+//   of its cache, the slots before it are pad.  With T cached slots and L new tokens in slots T .. T + L - 1:
+//     * the new k / v rows are appended at slots T + i whatever s is (pad tokens included: nobody reads them);
+//     * a query in a pad slot (T + i < s) reads nothing and writes an all-zero output row;
+//     * every other query attends to the slots [s, T + i] and to nothing else -- as a shift: the cache base moves forward by
+//       min(s, T) rows, T shrinks by as much, the first max(s - T, 0) tokens of the call are dropped from the key range, and the
+//       row then runs EXACTLY the arithmetic (same order of additions) of an unpadded row holding T - min(s, T) cached tokens.
+//   row_start == NULL is a separate instantiation that does not know any of this.
+//
 // Design reference for the single-token kernel: MaskedMultiheadAttention
 // (R/cpp/tensorrt_llm/kernels/decoderMaskedMultiheadAttention/...Template.h:1195-2188): one
 // block per (head, sequence), q.K over the cache, block softmax, V accumulation.  Here:
@@ -40,7 +49,7 @@ constexpr int MAX_L = 4;                              // query tokens per call h
 // ------------------------------------------------------------------------------------------------
 // self-attention
 // ------------------------------------------------------------------------------------------------
-template <bool I8>
+template <bool I8, bool RS = false>
 __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
     // issue priority over the other groups' K/V stream waves (see gemm_skinny_kernel)
     __builtin_amdgcn_s_setprio(3);
@@ -61,13 +70,22 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
         if (b >= live_n) return;
         b = live_b;
     }
-    const int T = p.t_dev ? t_now : p.T;         // device-resident step counter (graph replay) or host value
+    const int Tabs = p.t_dev ? t_now : p.T;      // device-resident step counter (graph replay) or host value
+    // right-aligned rows: `shift` pad slots in front of the cached rows, `i0` pad tokens at the head of this call (both 0 without RS)
+    int shift = 0, i0 = 0;
+    if constexpr (RS) {
+        const int rs = max(p.row_start[b], 0);
+        shift = min(rs, Tabs);
+        i0 = min(rs - shift, p.L);
+    }
+    const int T = Tabs - shift;                  // cached tokens the row sees
+    const size_t shift_b = (size_t)shift * (I8 ? 64 : 128);
     const int C = p.H * 64;
     // The kernel is a chain of dependent memory round trips (this call's q / k / v sums, the cached K rows, the cached V rows)
     // and at small batches nothing else: the first 64 K rows (one per lane) and the first 32 V rows (lane = dim) do not depend on
     // q, so they are requested before anything is waited for -- for T <= 32 cached tokens the whole kernel is one round trip.
-    const unsigned char* pastK0 = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(0 * p.H + h) * p.past_cap * 64) * (I8 ? 1 : 2);
-    const unsigned char* pastV0 = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(1 * p.H + h) * p.past_cap * 64) * (I8 ? 1 : 2);
+    const unsigned char* pastK0 = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(0 * p.H + h) * p.past_cap * 64) * (I8 ? 1 : 2) + shift_b;
+    const unsigned char* pastV0 = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(1 * p.H + h) * p.past_cap * 64) * (I8 ? 1 : 2) + shift_b;
     // (no per-element test around a load: hipcc would branch around each and wait for it before the next; rows past the
     // end re-read the last cached row instead, their values are never used)
     uint4 kpre[I8 ? 4 : 8];
@@ -123,8 +141,8 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
         s_knew[i][lane] = (h16)k;
         s_vnew[i][lane] = (h16)v;
         // append to the cache (present), position T + i
-        const size_t off_k = (size_t)b * p.present_bstride + ((size_t)(0 * p.H + h) * p.present_cap + T + i) * 64 + lane;
-        const size_t off_v = (size_t)b * p.present_bstride + ((size_t)(1 * p.H + h) * p.present_cap + T + i) * 64 + lane;
+        const size_t off_k = (size_t)b * p.present_bstride + ((size_t)(0 * p.H + h) * p.present_cap + Tabs + i) * 64 + lane;
+        const size_t off_v = (size_t)b * p.present_bstride + ((size_t)(1 * p.H + h) * p.present_cap + Tabs + i) * 64 + lane;
         if (I8) {
             ((int8_t*)p.present)[off_k] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(k * inv_t)));
             ((int8_t*)p.present)[off_v] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(v * inv_t)));
@@ -141,20 +159,26 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
     if (!inplace && T > 0) {
         const int es = I8 ? 1 : 2;
         for (int kv = 0; kv < 2; ++kv) {
-            const unsigned char* src = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(kv * p.H + h) * p.past_cap * 64) * es;
-            unsigned char* dst = (unsigned char*)p.present + ((size_t)b * p.present_bstride + (size_t)(kv * p.H + h) * p.present_cap * 64) * es;
+            const unsigned char* src = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(kv * p.H + h) * p.past_cap * 64) * es + shift_b;
+            unsigned char* dst = (unsigned char*)p.present + ((size_t)b * p.present_bstride + (size_t)(kv * p.H + h) * p.present_cap * 64) * es + shift_b;
             const int n16 = T * 64 * es / 16;
             for (int c = lane; c < n16; c += 64) ((uint4*)dst)[c] = ((const uint4*)src)[c];
         }
     }
     __syncthreads();
 
-    const unsigned char* pastK = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(0 * p.H + h) * p.past_cap * 64) * (I8 ? 1 : 2);
-    const unsigned char* pastV = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(1 * p.H + h) * p.past_cap * 64) * (I8 ? 1 : 2);
+    const unsigned char* pastK = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(0 * p.H + h) * p.past_cap * 64) * (I8 ? 1 : 2) + shift_b;
+    const unsigned char* pastV = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(1 * p.H + h) * p.past_cap * 64) * (I8 ? 1 : 2) + shift_b;
 
     for (int i = 0; i < p.L; ++i) {
+        if constexpr (RS) {
+            if (i < i0) {                         // a query in a pad slot (wave-uniform): zeros, nothing read
+                p.out[(size_t)(b * p.L + i) * p.ldo + h * 64 + lane] = (h16)0.f;
+                continue;
+            }
+        }
         const h16* s_q = s_qall[i];
-        const int nk = T + i + 1;                 // causal: past + new tokens 0..i
+        const int nk = T + (i - i0) + 1;          // causal: past + new tokens i0..i (i0 = 0 unless the call begins in a row's pad)
         // ---- scores: lane-per-key -------------------------------------------------------------
         float mx = -INFINITY;
         for (int j0 = 0; j0 < nk; j0 += 64) {
@@ -187,7 +211,7 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
                         }
                     }
                 } else {
-                    const h16* kn = s_knew[j - T];
+                    const h16* kn = s_knew[j - T + i0];
 #pragma unroll 8
                     for (int e = 0; e < 64; ++e) acc = fmaf((float)s_q[e], r16((float)kn[e] * ATTN_SCALE), acc);
                 }
@@ -255,7 +279,7 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
             }
             for (; j < T; ++j) o = fmaf(s_p[j], (float)pv[(size_t)j * 64], o);
         }
-        for (; j < nk; ++j) o = fmaf(s_p[j], (float)s_vnew[j - T][lane], o);
+        for (; j < nk; ++j) o = fmaf(s_p[j], (float)s_vnew[j - T + i0][lane], o);
         p.out[(size_t)(b * p.L + i) * p.ldo + h * 64 + lane] = (h16)f32_as_is(o);
         __syncthreads();
     }
@@ -273,7 +297,7 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
 // one-wave form (scores, probabilities and the dequantised cache values are rounded to fp16, sums are fp32); the fp32 additions
 // of the softmax sum and of P.V happen in a different order, so the two forms agree to fp32 rounding, not bit for bit.
 constexpr int SELF_WAVES = 4;
-template <bool I8>
+template <bool I8, bool RS = false>
 __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfParams p) {
     __builtin_amdgcn_s_setprio(3);
     constexpr int MAXT = 512;
@@ -303,10 +327,19 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
         if (b >= live_n) return;
         b = live_b;
     }
-    const int T = p.t_dev ? t_now : p.T;
+    const int Tabs = p.t_dev ? t_now : p.T;
+    int shift = 0, i0 = 0;                        // right-aligned rows: pad slots before the cached rows, pad tokens at the head of the call (see attn_self_kernel)
+    if constexpr (RS) {
+        const int rs = max(p.row_start[b], 0);
+        shift = min(rs, Tabs);
+        i0 = min(rs - shift, p.L);
+    }
+    const int T = Tabs - shift;
+    const size_t shift_b = (size_t)shift * ROW_B;
     const int C = p.H * 64;
     const unsigned char* pastK = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(0 * p.H + h) * p.past_cap * 64) * ES;
     const unsigned char* pastV = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(1 * p.H + h) * p.past_cap * 64) * ES;
+    if constexpr (RS) { pastK += shift_b; pastV += shift_b; }
     // rows past the end re-read the last cached row (no branch around a load); their values are never used
     const int vr = lane / NCH, vc = lane % NCH;   // V loads: row inside the block, 16-byte chunk of the row
     uint4 kpre[KCH], vpre[VPRE];
@@ -361,8 +394,8 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
             s_knew[i][lane] = (h16)k;
             s_vnew[i][lane] = (h16)v;
             if constexpr (I8) s_lut[512 + i * 64 + lane] = r16(k * ATTN_SCALE);      // (k is an fp16 value already)
-            const size_t off_k = (size_t)b * p.present_bstride + ((size_t)(0 * p.H + h) * p.present_cap + T + i) * 64 + lane;
-            const size_t off_v = (size_t)b * p.present_bstride + ((size_t)(1 * p.H + h) * p.present_cap + T + i) * 64 + lane;
+            const size_t off_k = (size_t)b * p.present_bstride + ((size_t)(0 * p.H + h) * p.present_cap + Tabs + i) * 64 + lane;
+            const size_t off_v = (size_t)b * p.present_bstride + ((size_t)(1 * p.H + h) * p.present_cap + Tabs + i) * 64 + lane;
             if (I8) {
                 ((int8_t*)p.present)[off_k] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(k * inv_t)));
                 ((int8_t*)p.present)[off_v] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(v * inv_t)));
@@ -377,8 +410,8 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
     const bool inplace = (p.past == p.present) && (p.past_cap == p.present_cap) && (p.past_bstride == p.present_bstride);
     if (!inplace && T > 0) {
         for (int kv = 0; kv < 2; ++kv) {
-            const unsigned char* src = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(kv * p.H + h) * p.past_cap * 64) * ES;
-            unsigned char* dst = (unsigned char*)p.present + ((size_t)b * p.present_bstride + (size_t)(kv * p.H + h) * p.present_cap * 64) * ES;
+            const unsigned char* src = (const unsigned char*)p.past + ((size_t)b * p.past_bstride + (size_t)(kv * p.H + h) * p.past_cap * 64) * ES + shift_b;
+            unsigned char* dst = (unsigned char*)p.present + ((size_t)b * p.present_bstride + (size_t)(kv * p.H + h) * p.present_cap * 64) * ES + shift_b;
             const int n16 = T * 64 * ES / 16;
             for (int c = tid; c < n16; c += NT) ((uint4*)dst)[c] = ((const uint4*)src)[c];
         }
@@ -386,8 +419,14 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
     __syncthreads();
 
     for (int i = 0; i < p.L; ++i) {
+        if constexpr (RS) {
+            if (i < i0) {                         // a query in a pad slot (workgroup-uniform): zeros, nothing read
+                if (wid == 0) p.out[(size_t)(b * p.L + i) * p.ldo + h * 64 + lane] = (h16)0.f;
+                continue;
+            }
+        }
         const h16* s_q = s_qall[i];
-        const int nk = T + i + 1;                 // causal: past + new tokens 0..i
+        const int nk = T + (i - i0) + 1;          // causal: past + new tokens i0..i (i0 = 0 unless the call begins in a row's pad)
         // ---- scores: key blocks of 64 dealt over the waves, a key per lane ------------------------------------------------
         float mx = -INFINITY;
         for (int kb = wid; kb * 64 < nk; kb += SELF_WAVES) {
@@ -399,7 +438,7 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
                 // were a second pass behind the cached keys' for a handful of lanes.  Same factors, same order of additions.
                 float acc = 0.f;
                 const bool cached = j < T;
-                const int jn = cached ? 0 : j - T;
+                const int jn = cached ? 0 : j - T + i0;
                 const uint4* kr = (const uint4*)(pastK + (size_t)min(j, max(T - 1, 0)) * ROW_B);
 #pragma unroll
                 for (int c = 0; c < KCH; ++c) {
@@ -483,7 +522,7 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
             for (int w = 0; w < SELF_WAVES; ++w)
 #pragma unroll
                 for (int r = 0; r < VROWS; ++r) acc += part[w][r];
-            for (int j = T; j < nk; ++j) acc = fmaf(s_p[j], (float)s_vnew[j - T][lane], acc);
+            for (int j = T; j < nk; ++j) acc = fmaf(s_p[j], (float)s_vnew[j - T + i0][lane], acc);
             p.out[(size_t)(b * p.L + i) * p.ldo + h * 64 + lane] = (h16)f32_as_is(acc);
         }
         __syncthreads();
@@ -496,7 +535,15 @@ int launch_attn_self(const AttnSelfParams& p, hipStream_t stream) {
     WM_REQUIRE(p.T + p.L <= p.present_cap, "attn_self: present capacity %d < T+L=%d", p.present_cap, p.T + p.L);
     WM_REQUIRE(!p.int8_kv || p.kv_scale > 0.f, "attn_self: int8 KV needs a positive scale");
     WM_REQUIRE(p.waves == 0 || p.waves == 1 || p.waves == SELF_WAVES, "attn_self: waves=%d (0, 1 or %d)", p.waves, SELF_WAVES);
-    if (p.waves == SELF_WAVES) {
+    if (p.row_start) {                           // right-aligned rows: the RS instantiations (the others do not read the field)
+        if (p.waves == SELF_WAVES) {
+            if (p.int8_kv) hipLaunchKernelGGL((attn_self_wg_kernel<true, true>), dim3(p.H, p.B), dim3(64 * SELF_WAVES), 0, stream, p);
+            else hipLaunchKernelGGL((attn_self_wg_kernel<false, true>), dim3(p.H, p.B), dim3(64 * SELF_WAVES), 0, stream, p);
+        } else if (p.int8_kv)
+            hipLaunchKernelGGL((attn_self_kernel<true, true>), dim3(p.H, p.B), dim3(64), 0, stream, p);
+        else
+            hipLaunchKernelGGL((attn_self_kernel<false, true>), dim3(p.H, p.B), dim3(64), 0, stream, p);
+    } else if (p.waves == SELF_WAVES) {
         if (p.int8_kv) hipLaunchKernelGGL(attn_self_wg_kernel<true>, dim3(p.H, p.B), dim3(64 * SELF_WAVES), 0, stream, p);
         else hipLaunchKernelGGL(attn_self_wg_kernel<false>, dim3(p.H, p.B), dim3(64 * SELF_WAVES), 0, stream, p);
     } else if (p.int8_kv)

@@ -916,6 +916,7 @@ struct GroupStep {
         const wm_dims& d = e->dims;
         EmbedParams ep{io->tokens, io->tokens_ld > 0 ? io->tokens_ld : L, M, L, e->emb_t, C,
                        (const h16*)io->positional_embedding, w.x, C, d.n_vocab, io->n_past_dev, nullptr};
+        ep.row_start = io->row_start; ep.T = T;
         ep.generation = chain ? w.generation : nullptr;      // the chain's granule epochs count the calls on this workspace
         if (chain) if (int rc = chain_prepare_workspace(s)) return rc;
         if (launch_embed(ep, s)) return 2;
@@ -1024,6 +1025,7 @@ struct GroupStep {
         p.amax = io->qkv_amax ? io->qkv_amax + i : nullptr;
         p.t_dev = io->n_past_dev;
         p.live = io->live_rows;
+        p.row_start = io->row_start;
         p.waves = self_attn_waves(M);
         layer_done = false;
         if (chain) {                   // the whole layer in one launch (a live-row list is not consulted: a one-row group is stepped while its
@@ -1172,7 +1174,8 @@ int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t str
         return 0;
     }
     GroupStep g;
-    if (int rc = g.init(e, io, s, !(io && io->not_alone))) return rc;
+    // (right-aligned rows: gemv_chain.hip's copy of the self-attention knows no row_start -- such a call is never `alone`)
+    if (int rc = g.init(e, io, s, !(io && (io->not_alone || io->row_start)))) return rc;
     if (g.begin(s)) return 2;
     for (int i = 0; i < e->dims.n_text_layer; ++i) {
         if (g.pre_cross(i, s)) return 2;
@@ -1189,6 +1192,7 @@ int wm_decoder_step_tap(const wm_engine* e, const wm_decoder_io* io, const wm_ta
     WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_step_tap: not a decoder engine");
     WM_REQUIRE(io && tap && tap->q_tape && tap->heads && tap->n_heads >= 1, "wm_decoder_step_tap: null argument");
     WM_REQUIRE(io->n_new >= 1 && io->n_new <= DEC_CHUNK && !io->n_past_dev, "wm_decoder_step_tap: n_new must be 1 .. %d, without a device step counter", DEC_CHUNK);
+    WM_REQUIRE(!io->row_start, "wm_decoder_step_tap: row_start (right-aligned rows) is not supported: word timestamps are computed without a prompt");
     const int H = e->dims.n_text_head, n_layer = e->dims.n_text_layer;
     WM_REQUIRE(H <= 64, "wm_decoder_step_tap: %d heads per layer (at most 64)", H);
     WM_REQUIRE(io->n_past >= 0 && tap->capacity >= io->n_past + io->n_new, "wm_decoder_step_tap: tape capacity %d < n_past + n_new = %d", tap->capacity,
@@ -1224,6 +1228,7 @@ int wm_decoder_step_multi(const wm_engine* e, int n_groups, const wm_decoder_io*
     GroupStep g[8];
     for (int k = 0; k < n_groups; ++k) {
         WM_REQUIRE(light_streams[k] && light_streams[k] != heavy_stream, "wm_decoder_step_multi: group %d needs its own stream", k);
+        WM_REQUIRE(!(ios[k] && ios[k]->row_start), "wm_decoder_step_multi: row_start (right-aligned rows) is not supported by the CU-partitioned schedule: use wm_decoder_step (group %d)", k);
         if (int rc = g[k].init(e, ios[k], (hipStream_t)light_streams[k], n_groups == 1 && !(ios[k] && ios[k]->not_alone))) return rc;
     }
     const int n_layer = e->dims.n_text_layer;
@@ -1590,6 +1595,21 @@ int wm_attn_decode_self(const float* qkv, int B, int L, int T, int H, const void
     if (T > 0 && past) { p.past = past; p.past_cap = past_cap; p.past_bstride = (long)2 * H * past_cap * 64; }
     else { p.past = present; p.past_cap = present_cap; p.past_bstride = p.present_bstride; }
     p.int8_kv = int8_kv; p.kv_scale = kv_scale; p.out = (h16*)out; p.ldo = H * 64;
+    p.waves = self_attn_waves(B * L);
+    return launch_attn_self(p, (hipStream_t)stream);
+}
+
+int wm_attn_decode_self_rows(const float* qkv, int B, int L, int T, int H, void* cache, int cap, int int8_kv, float kv_scale, void* out,
+                             const int32_t* row_start, const int32_t* live_rows, wm_stream_t stream) {
+    WM_REQUIRE(qkv && cache && out, "wm_attn_decode_self_rows: null argument");
+    WM_REQUIRE(B >= 1 && H >= 1 && T >= 0, "wm_attn_decode_self_rows: bad B/H/T (%d, %d, %d)", B, H, T);
+    AttnSelfParams p{};
+    p.part = qkv; p.ksplit = 1; p.ldp = 3 * H * 64; p.bias = nullptr;
+    p.B = B; p.L = L; p.T = T; p.H = H;
+    p.present = cache; p.present_cap = cap; p.present_bstride = (long)2 * H * cap * 64;
+    p.past = cache; p.past_cap = cap; p.past_bstride = p.present_bstride;            // in place, as the decode loop runs it
+    p.int8_kv = int8_kv; p.kv_scale = kv_scale; p.out = (h16*)out; p.ldo = H * 64;
+    p.row_start = row_start; p.live = live_rows;
     p.waves = self_attn_waves(B * L);
     return launch_attn_self(p, (hipStream_t)stream);
 }

@@ -161,6 +161,10 @@ struct EmbedParams {
     int n_vocab;
     const int32_t* t_dev;                    // optional device counter: token column / position row offset
     unsigned* generation;                    // optional: incremented once per call (the one-row chain's epoch counter)
+    // optional [B] (right-aligned rows, wm_decoder_io::row_start): the position row of absolute slot t of utterance b is
+    // t - row_start[b], pad slots (t < row_start[b]) take row 0.  `pos` is then the table's row T of a table that starts T rows
+    // before it (T: host value; with t_dev the table's base and T = 0 as ever)
+    const int32_t* row_start; int T;
 };
 int launch_embed(const EmbedParams& p, hipStream_t stream);
 
@@ -199,6 +203,10 @@ struct AttnSelfParams {
     h16* out; int ldo;                       // [M][C]
     const int32_t* live;                     // optional [1 + B]: count, then the rows to process (others are skipped)
     int waves;                               // waves per (b, h): 0 / 1 the one-wave kernel, 4 the workgroup form (small groups)
+    // optional [B] (right-aligned rows): utterance b's sequence begins at slot row_start[b] of its cache; the slots before it are
+    // pad: never read as keys, and a query in a pad slot writes zeros (attn_decode.hip states the contract).  NULL: every row
+    // begins at slot 0 -- the kernels instantiated for that case do not know the field
+    const int32_t* row_start;
 };
 int launch_attn_self(const AttnSelfParams& p, hipStream_t stream);
 

@@ -250,7 +250,13 @@ __global__ __launch_bounds__(256) void embed_kernel(EmbedParams p) {
     if (tok >= p.n_vocab) tok = p.n_vocab - 1;
     const int kt_total = p.C / 32;
     const unsigned char* base = (const unsigned char*)p.emb_tiles + (size_t)(tok >> 4) * kt_total * 1024 + (tok & 15) * 16;
-    const h16* pos = p.pos + (size_t)(m % p.L + T) * p.C;
+    long prow = m % p.L + T;
+    if (p.row_start) {                               // right-aligned rows: slot t of utterance b sits at position t - row_start[b]; pad slots take position 0
+        const int slot = (p.t_dev ? T : p.T) + m % p.L;
+        const int at = max(slot - max(p.row_start[m / p.L], 0), 0);      // 0 <= at <= slot: inside the table whatever the caller wrote
+        prow += at - slot;                           // (p.pos is row `slot - m % p.L` of the table: the rows before it exist)
+    }
+    const h16* pos = p.pos + prow * p.C;
     for (int piece = threadIdx.x; piece < p.C / 8; piece += blockDim.x) {
         const int kt = piece >> 2, g = piece & 3;
         const half8v e = *(const half8v*)(base + (size_t)kt * 1024 + g * 256);

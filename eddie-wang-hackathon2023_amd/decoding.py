@@ -318,9 +318,47 @@ class BeamSearchDecoder:
         return out_tokens, out_sums
 
 
+ROW_PAD_TOKEN = 0        # what the pad slots of a right-aligned row hold: any token but EOT (post_process cuts a row at its first EOT)
+
+
+def row_prompt_layout(n_text_ctx: int, sot_sequence: Sequence[int], sot: int) -> Tuple[int, int, int]:
+    """(L0, sot_index, prompt_capacity) of an instance with per-row prompts: every row of a call is L0 = n_text_ctx // 2 +
+    len(sot_sequence) tokens long whatever its prompt -- the room <|startofprev|> and upstream's longest prompt
+    (n_text_ctx // 2 - 1 tokens) need -- so `sample_begin` = L0 and `sot_index` are one value per instance."""
+    half = n_text_ctx // 2
+    return half + len(sot_sequence), half + list(sot_sequence).index(sot), half - 1
+
+
+def right_aligned_rows(prompts: Sequence[Sequence[int]], sot_sequence: Sequence[int], sot_prev: int, n_text_ctx: int,
+                       pad: int = ROW_PAD_TOKEN) -> Tuple[List[List[int]], List[int]]:
+    """The start rows of a call with a prompt per utterance, and where each row begins:
+
+        [pad x start[b]] [<|startofprev|> prompt_b[-(n_text_ctx // 2 - 1):]] [sot_sequence]
+
+    every row L0 tokens long (row_prompt_layout).  An empty prompt has no <|startofprev|>, as upstream (W/decoding.py:508-511):
+    its row begins at the sot_sequence.  The decoder treats slot start[b] of row b as position 0 (wm_decoder_io::row_start)."""
+    sot_sequence = [int(t) for t in sot_sequence]
+    L0, _, capacity = row_prompt_layout(n_text_ctx, sot_sequence, sot_sequence[0])
+    rows, starts = [], []
+    for prompt in prompts:
+        prompt = [int(t) for t in prompt]
+        body = ([int(sot_prev)] + prompt[-capacity:] if prompt else []) + sot_sequence
+        starts.append(L0 - len(body))
+        rows.append([int(pad)] * (L0 - len(body)) + body)
+    return rows, starts
+
+
 class WhisperDecoding:
     def __init__(self, engine_dir, only_torch: bool = False, vocab_path: Optional[str] = None,
-                 options: Optional[DecodingOptions] = None):
+                 options: Optional[DecodingOptions] = None, row_prompts: bool = False):
+        """`row_prompts`: every utterance of a main_loop call may carry a prompt of its own (`set_prompts`: the previous text of
+        long-form transcription, names and spellings).  The rows are right-aligned (`right_aligned_rows`): all of them are
+        L0 = n_text_ctx // 2 + len(sot_sequence) tokens long and `sample_begin`, `sot_index`, the buffers and the captured graphs
+        are fixed at construction; only where a row begins differs.  The price is the room for sampling: the effective
+        sample_len is min(sample_len, n_text_ctx - L0) -- a row with a full prompt is cut exactly where upstream cuts it, a row
+        with a short or no prompt loses at most len(sot_sequence) tokens against upstream's n_text_ctx // 2 (and pays for a
+        prefill of L0 tokens).  Device loop only (greedy, temperature, best_of, beam search); not with `options.prompt` /
+        `options.prefix`, not with `cu_partition`; word_timestamps stays prompt-free, as upstream."""
         engine_dir = Path(engine_dir)
         self.decoder_config = None
         self.cross_attn_config = None
@@ -350,6 +388,17 @@ class WhisperDecoding:
             self.initial_token_length = len(self.initial_tokens)
             self.tokens = torch.tensor([self.initial_tokens]).repeat(self.decoder_config['num_audio'], 1)
             self.sot_index = self.initial_tokens.index(self.tokenizer.sot)
+        self.row_prompts = bool(row_prompts)
+        self._prompts = None              # set_prompts: one token list per utterance of the next main_loop calls
+        if self.row_prompts:
+            if self.options.prompt or self.options.prefix:
+                raise ValueError("row_prompts: the prompt is per row (set_prompts); options.prompt / options.prefix are not supported with it")
+            n_ctx = self.decoder_config['num_text_ctx']
+            L0, self.sot_index, self.prompt_capacity = row_prompt_layout(n_ctx, self.sot_sequence, self.tokenizer.sot)
+            self.initial_tokens = tuple(right_aligned_rows([()], self.sot_sequence, self.tokenizer.sot_prev, n_ctx)[0][0])
+            self.initial_token_length = L0
+            self.tokens = torch.tensor([self.initial_tokens]).repeat(self.decoder_config['num_audio'], 1)
+            self.sample_len = min(self.sample_len, n_ctx - L0)
         self.sample_begin: int = len(self.initial_tokens)
         self.use_int8_kv_cache = self.decoder_config['use_int8_kv_cache']
         self.use_int8_cross_kv = bool(self.decoder_config.get('use_int8_cross_kv', False))     # opt-in, beyond the reference
@@ -739,12 +788,44 @@ class WhisperDecoding:
         self.tokens = torch.tensor([self.initial_tokens]).repeat(len(language_tokens), 1)
         self.tokens[:, self.sot_index + 1] = torch.tensor(language_tokens, dtype=self.tokens.dtype)
 
+    def set_prompts(self, prompts: Optional[Sequence[Sequence[int]]]) -> None:
+        """Hand in the prompt (token ids) of every utterance of the next main_loop calls -- the previous windows' text of a
+        file, names and spellings -- for an instance built with `row_prompts=True`.  A prompt's last n_text_ctx // 2 - 1
+        tokens are used, behind <|startofprev|>; an empty one leaves its row without <|startofprev|>, as upstream.  The prompts
+        stay in force until they are set again (None: no prompts); they compose with `set_language_tokens` /
+        `detect_language` in either order.  A main_loop call over another number of utterances is refused."""
+        if not self.row_prompts:
+            raise ValueError("set_prompts: needs an instance built with row_prompts=True (the start length is fixed at construction)")
+        if prompts is None:
+            self._prompts = None
+            return
+        prompts = [[int(t) for t in p] for p in prompts]
+        V = self.decoder_config['vocab_size']
+        if not prompts or any(t < 0 or t >= V for p in prompts for t in p):
+            raise ValueError("set_prompts: need one list of token ids of the vocabulary per utterance")
+        self._prompts = prompts
+
     # ---- decoding loops ---------------------------------------------------------------------------------
     def _initial_token_rows(self, n_audio, device):
         tokens = self.tokens
         if tokens.shape[0] != n_audio:
             tokens = torch.tensor([self.initial_tokens]).repeat(n_audio, 1)
+        if self.row_prompts:
+            # the rows so far carry the sot_sequence (with its language token) at their right end; the prompts go in front of it
+            n_sot = len(self.sot_sequence)
+            prompts = self._prompts if self._prompts is not None else [()] * n_audio
+            if len(prompts) != n_audio:
+                raise ValueError(f"set_prompts gave {len(prompts)} prompts, this call decodes {n_audio} utterances")
+            rows, starts = right_aligned_rows(prompts, self.sot_sequence, self.tokenizer.sot_prev, self.decoder_config['num_text_ctx'])
+            tokens = tokens.clone()
+            tokens[:, :-n_sot] = torch.tensor(rows, dtype=tokens.dtype)[:, :-n_sot]
+            self._row_starts = torch.tensor(starts, dtype=torch.int32).repeat_interleave(self.n_group)
         return tokens.repeat_interleave(self.n_group, dim=0).to(device)
+
+    def _refuse_row_prompts(self, what: str) -> None:
+        if self.row_prompts:
+            raise ValueError(f"{what}: an instance built with row_prompts=True decodes through the device loop only "
+                             "(main_loop with features on the GPU, device_sampling on)")
 
     def _host_step(self, i, logits, tokens, sum_logprobs, no_speech_probs):
         if i == 0 and self.tokenizer.no_speech is not None:       # save no_speech_probs
@@ -759,6 +840,7 @@ class WhisperDecoding:
     def main_loop_reference(self, audio_features):
         """The reference's loop verbatim in structure (W/decoding.py:785-821): one `decode()` per token,
         host-side filters, concat KV."""
+        self._refuse_row_prompts("main_loop_reference")
         tokens = self._initial_token_rows(audio_features.shape[0], audio_features.device)
         n_batch = tokens.shape[0]
         sum_logprobs: Tensor = torch.zeros(n_batch, device=audio_features.device)
@@ -781,6 +863,7 @@ class WhisperDecoding:
 
     def torch_main_loop(self, model, audio_features):
         """PyTorch path (W/decoding.py:743-783): `model.decoder(tokens, xa, kv_cache=)` with hooks."""
+        self._refuse_row_prompts("torch_main_loop")
         with torch.no_grad():
             tokens = self._initial_token_rows(audio_features.shape[0], audio_features.device)
             n_batch = tokens.shape[0]
@@ -856,6 +939,8 @@ class WhisperDecoding:
             live={},
             # per-row sample_len (stable address: the captured graphs read it); 2^30 = no limit
             row_limit=torch.full((n_batch,), 1 << 30, dtype=torch.int32, device=device),
+            # per-row first slot (row_prompts; stable address: the captured graphs read it)
+            row_start=torch.zeros(n_batch, dtype=torch.int32, device=device) if self.row_prompts else None,
             suppress=torch.tensor(suppress or [0], dtype=torch.int32, device=device), n_suppress=len(suppress),
             blank=torch.tensor(blank or [0], dtype=torch.int32, device=device), n_blank=len(blank),
         )
@@ -1152,6 +1237,10 @@ class WhisperDecoding:
         n_micro, bounds = self._groups(n_batch)
         if self.cu_partition and n_micro > 1 and self.beam:
             raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
+        if self.cu_partition and n_micro > 1 and self.row_prompts:
+            raise ValueError("row_prompts is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
+        if self.row_prompts:
+            st['row_start'].copy_(self._row_starts)
         if self.cu_partition and n_micro > 1 and self.decoder_session.qkv_amax is None and row_limit is None and temp == self.options.temperature:
             return self._main_loop_partitioned(audio_features, st, cross, L0, n_micro, bounds, ignore_eot)
         use_live = bool(self.skip_finished_rows) and not ignore_eot and max(hi - lo for lo, hi in bounds) <= 1024
@@ -1163,7 +1252,8 @@ class WhisperDecoding:
             groups.append(dict(lo=lo, hi=hi, stream=streams[g].cuda_stream, slot=g, active=True,
                                kv=[t[lo:hi] for t in st['kv']], cross=[t[lo:hi] for t in cross],
                                logits=st['logits'][lo:hi], tokens=st['tokens'][lo:hi], done=st['done'][lo:hi],
-                               live=self._live_list(st, n_micro, g, lo, hi) if use_live else None))
+                               live=self._live_list(st, n_micro, g, lo, hi) if use_live else None,
+                               row_start=st['row_start'][lo:hi] if self.row_prompts else None))
             if self.beam:       # the group's cache rows per layer as a device-resident pointer table (wm_kv_reorder; stable like the buffers)
                 if (n_micro, g) not in st['kv_tables']:
                     st['kv_tables'][(n_micro, g)] = torch.tensor([t.data_ptr() for t in groups[-1]['kv']], dtype=torch.int64, device=dev)
@@ -1217,7 +1307,7 @@ class WhisperDecoding:
 
                     def issue_prefill(gr=gr, lo=lo, hi=hi, sm=sm, slot=slot):
                         sess.decoder_step(gr['tokens'][:, :L0], pos[0:L0], gr['cross'], None, cap, gr['kv'], cap,
-                                          gr['logits'], 0, sm, slot=slot, live_rows=gr['live'], not_alone=shared)
+                                          gr['logits'], 0, sm, slot=slot, live_rows=gr['live'], not_alone=shared, row_start=gr['row_start'])
                         token_step(gr, gr['logits'].data_ptr() + (L0 - 1) * V * 2, L0 * V, L0, sm)
                         finish_step(gr, None)
                     if use_graph and self.graph_prefill and pkey in st['graphs']:
@@ -1237,7 +1327,8 @@ class WhisperDecoding:
                         st['graphs'][gkey].replay()
                 else:
                     sess.decoder_step(gr['tokens'][:, cur - 1:cur], pos[cur - 1:cur], gr['cross'], gr['kv'], cap,
-                                      gr['kv'], cap, gr['logits'], cur - 1, sm, slot=slot, live_rows=gr['live'], not_alone=shared)
+                                      gr['kv'], cap, gr['logits'], cur - 1, sm, slot=slot, live_rows=gr['live'], not_alone=shared,
+                                      row_start=gr['row_start'])
                     token_step(gr, gr['logits'].data_ptr(), V, cur, sm)
                     finish_step(gr, None)
                     if use_graph:
@@ -1257,7 +1348,7 @@ class WhisperDecoding:
                         with native.CAPTURE_LOCK, torch.cuda.graph(graph, stream=streams[slot], capture_error_mode="thread_local"):
                             sess.decoder_step(gr['tokens'], pos, gr['cross'], gr['kv'], cap, gr['kv'], cap,
                                               gr['logits'], 1, sm, slot=slot, n_past_dev=counter, n_new=1, live_rows=gr['live'],
-                                              not_alone=shared)
+                                              not_alone=shared, row_start=gr['row_start'])
                             token_step(gr, gr['logits'].data_ptr(), V, 0, sm, n_past_dev=counter)
                             finish_step(gr, counter)
                         st['graphs'][gkey], st['counters'][gkey] = graph, counter

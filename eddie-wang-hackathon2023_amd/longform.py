@@ -15,6 +15,13 @@ the timestamp token tb + k means k * 2 * fs seconds, 2 * k frames.
 
 One deliberate difference from upstream: an advance that is <= 0 or > segment_size becomes segment_size.  Upstream stands still
 for ever on <|0.00|><|0.00|>, and with random weights the timestamp indices run past the window.
+
+Prompts (`condition_on_previous_text`, `initial_prompt`: DESIGN.md section 5f).  Upstream's rules, kept by `PromptHistory` per
+file: the history starts as the initial prompt; a window is decoded with history[reset_since:] as its prompt (the decoder keeps
+the last n_text_ctx // 2 - 1 of them); a window that settles appends its segments' tokens, timestamp tokens included, and then
+forgets everything so far (reset_since = len(history)) when conditioning is off or the standing result was drawn above
+temperature 0.5; a skipped window changes nothing.  Every call of a window's ladder sees the same prompt.  With neither option
+set the decoder callbacks are called exactly as before; with either they receive the prompt(s) as one more argument.
 """
 from __future__ import annotations
 
@@ -144,6 +151,26 @@ def settle_window(result, tb: int, seek: int, segment_size: int, fs: float, th: 
     return segments, advance
 
 
+class PromptHistory:
+    """The tokens a file's later windows are conditioned on (module docstring)."""
+
+    def __init__(self, initial_prompt: Sequence[int] = (), condition_on_previous_text: bool = False):
+        self.tokens: List[int] = [int(t) for t in initial_prompt]
+        self.reset_since = 0
+        self.condition = bool(condition_on_previous_text)
+
+    def prompt(self) -> List[int]:
+        return self.tokens[self.reset_since:]
+
+    def settle(self, result, segments: Sequence[dict], skipped: bool) -> None:
+        """After a window whose `result` stands and was cut into `segments` (or skipped)."""
+        if skipped:
+            return
+        self.tokens += [int(t) for s in segments for t in s["tokens"]]
+        if not self.condition or float(result.temperature) > 0.5:
+            self.reset_since = len(self.tokens)
+
+
 def _thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold) -> Thresholds:
     return Thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold)
 
@@ -158,9 +185,13 @@ def _check_ladder(temperatures: Sequence[float]) -> Tuple[float, ...]:
 def transcribe_reference(decode_one: Callable[[int, float], object], content_frames: int, *, window: int, timestamp_begin: int,
                          temperatures: Sequence[float] = TEMPERATURES, compression_ratio_threshold: Optional[float] = 2.4,
                          logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
-                         decode_text: Optional[Callable[[List[int]], str]] = None) -> List[dict]:
-    """The literal loop for one file of `content_frames` frames: `decode_one(seek, temperature)` decodes the window at `seek`."""
+                         decode_text: Optional[Callable[[List[int]], str]] = None, condition_on_previous_text: bool = False,
+                         initial_prompt: Sequence[int] = ()) -> List[dict]:
+    """The literal loop for one file of `content_frames` frames: `decode_one(seek, temperature)` decodes the window at `seek`.
+    With `condition_on_previous_text` or an `initial_prompt` (token ids): `decode_one(seek, temperature, prompt)`."""
     temperatures = _check_ladder(temperatures)
+    prompted = bool(condition_on_previous_text) or len(initial_prompt) > 0
+    history = PromptHistory(initial_prompt, condition_on_previous_text)
     th = _thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold)
     fs = CHUNK_LENGTH / window
     segments: List[dict] = []
@@ -168,11 +199,13 @@ def transcribe_reference(decode_one: Callable[[int, float], object], content_fra
     while seek < content_frames:
         segment_size = min(window, content_frames - seek)
         result = None
+        prompt = history.prompt()
         for t in temperatures:                         # the ladder: the first result that passes stands, else the last
-            result = decode_one(seek, t)
+            result = decode_one(seek, t, list(prompt)) if prompted else decode_one(seek, t)
             if not needs_fallback(result, *_astuple(th)):
                 break
         cut, advance = settle_window(result, timestamp_begin, seek, segment_size, fs, th, decode_text)
+        history.settle(result, cut, skip_window(result, th.logprob_threshold, th.no_speech_threshold))
         segments += cut
         seek += advance
     return segments
@@ -186,7 +219,8 @@ def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], f
                        content_frames_list: Sequence[int], n_rows: int, *, window: int, timestamp_begin: int,
                        temperatures: Sequence[float] = TEMPERATURES, compression_ratio_threshold: Optional[float] = 2.4,
                        logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
-                       decode_text: Optional[Callable[[List[int]], str]] = None) -> List[List[dict]]:
+                       decode_text: Optional[Callable[[List[int]], str]] = None, condition_on_previous_text: bool = False,
+                       initial_prompt: Sequence[int] = ()) -> List[List[dict]]:
     """The scheduler: up to `n_rows` files are active, one row each; every round decodes the current window of each.
 
     `decode_call(rows, temperature, live)`: rows[i] = (file, seek) of row i or None for an empty row, always n_rows of them;
@@ -194,7 +228,11 @@ def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], f
     at temperatures[0] with every occupied row live, then, for each further temperature while any row still needs it, one call
     in which only those rows are live (the rows are the round's: same files, same seeks).  A call carries one temperature, and
     no (file, seek, temperature) is asked twice.  A finished file's row goes to the next waiting file from the following round
-    on; files without content never take a row.  Per file the segments equal `transcribe_reference`'s for the same decoder."""
+    on; files without content never take a row.  Per file the segments equal `transcribe_reference`'s for the same decoder.
+
+    With `condition_on_previous_text` or an `initial_prompt` (token ids, the same for every file):
+    `decode_call(rows, temperature, live, prompts)`, prompts[i] the prompt of row i's window ([] for an empty row); the fallback
+    calls of a round carry the round's prompts."""
     temperatures = _check_ladder(temperatures)
     if n_rows < 1:
         raise ValueError(f"n_rows = {n_rows}: need at least one row")
@@ -205,21 +243,27 @@ def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], f
     waiting = deque(f for f, c in enumerate(content) if c > 0)
     rows: List[Optional[int]] = [None] * n_rows        # the file of every row
     seek: Dict[int, int] = {}
+    prompted = bool(condition_on_previous_text) or len(initial_prompt) > 0
+    history: Dict[int, PromptHistory] = {}
     while True:
         for i in range(n_rows):
             if rows[i] is None and waiting:
                 rows[i] = waiting.popleft()
                 seek[rows[i]] = 0
+                history[rows[i]] = PromptHistory(initial_prompt, condition_on_previous_text)
         if all(f is None for f in rows):
             break
         asked = [None if f is None else (f, seek[f]) for f in rows]
         live = [f is not None for f in rows]
-        final = list(decode_call(list(asked), temperatures[0], list(live)))
+        prompts = [[] if f is None else history[f].prompt() for f in rows]
+        extra = ([list(p) for p in prompts],) if prompted else ()
+        final = list(decode_call(list(asked), temperatures[0], list(live), *extra))
         need = [live[i] and needs_fallback(final[i], *_astuple(th)) for i in range(n_rows)]
         for t in temperatures[1:]:
             if not any(need):
                 break
-            again = decode_call(list(asked), t, list(need))
+            extra = ([list(p) for p in prompts],) if prompted else ()
+            again = decode_call(list(asked), t, list(need), *extra)
             for i in range(n_rows):
                 if need[i]:
                     final[i] = again[i]
@@ -229,6 +273,7 @@ def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], f
                 continue
             segment_size = min(window, content[f] - seek[f])
             cut, advance = settle_window(final[i], timestamp_begin, seek[f], segment_size, fs, th, decode_text)
+            history[f].settle(final[i], cut, skip_window(final[i], th.logprob_threshold, th.no_speech_threshold))
             segments[f] += cut
             seek[f] += advance
             if seek[f] >= content[f]:

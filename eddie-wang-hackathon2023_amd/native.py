@@ -82,7 +82,7 @@ EXPORTS = (
     "wm_beam_workspace_bytes", "wm_beam_step", "wm_kv_reorder",
     "wm_gemm_ex", "wm_row_finish", "wm_embed", "wm_mel_transpose_pad", "wm_zero_pad_rows",
     "wm_decoder_step_tap", "wm_align_workspace_bytes", "wm_align", "wm_dtw_workspace_bytes", "wm_dtw",
-    "wm_mel_windows", "wm_resample",
+    "wm_mel_windows", "wm_resample", "wm_attn_decode_self_rows",
 )
 
 
@@ -141,6 +141,7 @@ class WmDecoderIO(C.Structure):
         ("live_rows", C.c_void_p),
         ("workspace_id", C.c_uint64),
         ("not_alone", C.c_int32),
+        ("row_start", C.c_void_p),
     ]
 
 
@@ -318,6 +319,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_attn_encoder.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp]
     lib.wm_attn_decode_cross.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp]
     lib.wm_attn_decode_self.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, C.c_float, vp, vp]
+    lib.wm_attn_decode_self_rows.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, C.c_float, vp, vp, vp, vp]
     lib.wm_quantize_i8.argtypes = [vp, vp, C.c_int64, C.c_float, vp]
     lib.wm_log_mel_workspace_bytes.argtypes = [i32, i32, i32]
     lib.wm_log_mel_workspace_bytes.restype = sz

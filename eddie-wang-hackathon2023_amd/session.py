@@ -213,7 +213,8 @@ class Session(object):
                         present: Sequence[torch.Tensor], present_capacity: int, logits: torch.Tensor,
                         n_past: int, qkv_amax: Optional[torch.Tensor] = None, slot: int = 0,
                         n_past_dev: Optional[torch.Tensor] = None, n_new: Optional[int] = None,
-                        live_rows: Optional[torch.Tensor] = None, not_alone: bool = False) -> WmDecoderIO:
+                        live_rows: Optional[torch.Tensor] = None, not_alone: bool = False,
+                        row_start: Optional[torch.Tensor] = None) -> WmDecoderIO:
         """The wm_decoder_io of one call.  tokens int32 [B, L] (any row stride: a column window of a wider
         buffer works); past/present per layer [B,2,H,capacity,64]; present may be the same tensors as past
         (in-place append).  The struct keeps its pointer arrays alive (`io._keep`)."""
@@ -251,13 +252,17 @@ class Session(object):
             assert live_rows.dtype == torch.int32 and live_rows.numel() >= 1 + b and live_rows.is_contiguous()
         io.live_rows = live_rows.data_ptr() if live_rows is not None else None
         io.not_alone = 1 if not_alone else 0      # other groups' steps in flight beside this one: never a one-launch form (whisper_mi355.h)
-        io._keep = (past_arr, present_arr, cross_arr, ws, live_rows)
+        if row_start is not None:      # int32 [B]: the slot each row's sequence begins at (right-aligned rows, whisper_mi355.h)
+            assert row_start.dtype == torch.int32 and row_start.numel() == b and row_start.is_contiguous()
+        io.row_start = row_start.data_ptr() if row_start is not None else None
+        io._keep = (past_arr, present_arr, cross_arr, ws, live_rows, row_start)
         return io
 
     def decoder_step(self, tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
-                     stream: int, qkv_amax=None, slot: int = 0, n_past_dev=None, n_new=None, live_rows=None, not_alone: bool = False):
+                     stream: int, qkv_amax=None, slot: int = 0, n_past_dev=None, n_new=None, live_rows=None, not_alone: bool = False,
+                     row_start=None):
         io = self.make_decoder_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
-                                  qkv_amax, slot, n_past_dev, n_new, live_rows, not_alone)
+                                  qkv_amax, slot, n_past_dev, n_new, live_rows, not_alone, row_start)
         check(self._engine.lib.wm_decoder_step(self._engine.handle, C.byref(io), stream), "wm_decoder_step")
 
     def decoder_step_tap(self, tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past, stream: int,

@@ -15,13 +15,18 @@ longform.py states the contract (the rules and the schedule, on the host, tested
     WhisperDecoding free and re-allocate its whole buffer set and its graphs;
   * a file's language is detected on its first window (unless the options name one) and kept for all of its windows.
 
-Refused in this version (ValueError): an instance built with `prompt` / `prefix`, `condition_on_previous_text` (the rows of a
-batch share one start length), and beam_size / best_of together with a ladder of more than one temperature.  Out of scope: word
+  * `condition_on_previous_text` / `initial_prompt` (upstream's options; default here: off -- upstream's default is on): every
+    file carries its own history (longform.PromptHistory), a round hands the decoder one prompt per row
+    (WhisperDecoding.set_prompts: right-aligned rows).  They need an instance built with `row_prompts=True`, whose start
+    length is fixed at construction.
+
+Refused (ValueError): an instance built with `prompt` / `prefix` (use `initial_prompt`), conditioning or an initial prompt on
+an instance without `row_prompts`, and beam_size / best_of together with a ladder of more than one temperature.  Out of scope: word
 timestamps per segment, clip_timestamps, the hallucination-silence heuristics.  Files at any rate from 4 kHz to 192 kHz and with
 several channels are downmixed and resampled to 16 kHz on the device (whisper_utils.load_audio_device, wm_resample).
 
 CLI: python transcribe.py --engine_dir eng --input_file a.flac [b.flac ...] --vocab multilingual.tiktoken [--temperature T ...]
-[--no_fallback] prints one "[mm:ss.mmm --> mm:ss.mmm] text" line per non-empty segment.
+[--no_fallback] [--condition_on_previous_text] [--initial_prompt TEXT] prints one "[mm:ss.mmm --> mm:ss.mmm] text" line per non-empty segment.
 """
 from __future__ import annotations
 
@@ -40,14 +45,16 @@ from encoding import WhisperEncoding
 from tokenizer import Tokenizer
 
 
-def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], condition_on_previous_text: bool = False) -> None:
+def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], condition_on_previous_text: bool = False,
+                    initial_prompt=None) -> None:
     """The combinations this version refuses (module docstring)."""
     opt = decoding.options
     if opt.prompt or opt.prefix:
-        raise ValueError("transcribe: an instance built with prompt / prefix is not supported in this version")
-    if condition_on_previous_text:
-        raise ValueError("transcribe: condition_on_previous_text is not supported in this version "
-                         "(the rows of a batch share one start length)")
+        raise ValueError("transcribe: an instance built with options.prompt / options.prefix is not supported: hand the prompt to "
+                         "transcribe(initial_prompt=...) with an instance built with row_prompts=True")
+    if (condition_on_previous_text or initial_prompt) and not getattr(decoding, 'row_prompts', False):
+        raise ValueError("transcribe: condition_on_previous_text / initial_prompt need a WhisperDecoding built with row_prompts=True "
+                         "(every row carries its own prompt; the start length is fixed at construction)")
     if decoding.beam or decoding.n_group != 1:
         if len(temperatures) != 1 or float(temperatures[0]) != float(opt.temperature):
             raise ValueError("transcribe: beam_size / best_of decode at the instance's temperature: give that one temperature "
@@ -87,14 +94,21 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
                    content_frames: Sequence[int], *, temperatures: Sequence[float] = longform.TEMPERATURES,
                    compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
                    no_speech_threshold: Optional[float] = 0.6, n_rows: Optional[int] = None, trace: Optional[list] = None,
-                   condition_on_previous_text: bool = False) -> List[dict]:
+                   condition_on_previous_text: bool = False, initial_prompt=None) -> List[dict]:
     """Transcribe files given as log-mels: mels[f] fp16 [n_mels, content_frames[f] + W] on the GPU (W = 2 * n_audio_ctx; the last
     W frames are the log-mel of 30 s of padding: whisper_utils.long_log_mel_device).  One dict per file: language, text, segments;
     a segment: seek, start, end (seconds), text, tokens, temperature, avg_logprob, compression_ratio, no_speech_prob.
     `n_rows`: rows of every decoder call (default: min(files, what fits)).  `trace`: a list that receives one dict per decoder
-    call (rows, live, temperature, windows, results, ...: tests, diagnostics)."""
+    call (rows, live, temperature, windows, results, prompts, ...: tests, diagnostics).
+    `condition_on_previous_text`: every window of a file is decoded with the file's text so far as its prompt (upstream's rules,
+    longform.py; off by default, unlike upstream).  `initial_prompt`: a string or token ids, the prompt of every file's first
+    window (and, with conditioning, the head of its history)."""
     temperatures = tuple(float(t) for t in (temperatures if isinstance(temperatures, (tuple, list)) else [temperatures]))
-    check_supported(decoding, temperatures, condition_on_previous_text)
+    check_supported(decoding, temperatures, condition_on_previous_text, initial_prompt)
+    if isinstance(initial_prompt, str):
+        initial_prompt = decoding.tokenizer.encode(" " + initial_prompt.strip())
+    initial_prompt = [int(t) for t in (initial_prompt if initial_prompt is not None else ())]
+    prompted = bool(condition_on_previous_text) or len(initial_prompt) > 0
     n_files = len(mels)
     if len(content_frames) != n_files:
         raise ValueError(f"transcribe: {len(content_frames)} content_frames for {n_files} mels")
@@ -143,7 +157,7 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
         else:
             state['languages'], state['tokens'] = ['en'] * len(rows), None
 
-    def decode_call(rows, temperature, live):
+    def decode_call(rows, temperature, live, prompts=None):
         assert len(rows) == n_rows and len(live) == n_rows
         new_round = state['rows'] != list(rows)
         if new_round:
@@ -151,6 +165,8 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
         features = state['features']
         if state['tokens'] is not None:
             decoding.set_language_tokens(state['tokens'])
+        if getattr(decoding, 'row_prompts', False):
+            decoding.set_prompts(prompts)                # (None without conditioning / an initial prompt: every row starts bare)
         limit = torch.tensor([(1 << 30) if on else 0 for on in live], dtype=torch.int32).repeat_interleave(n_group)
         per_call = None if (decoding.beam or n_group != 1) else temperature
         tokens, sum_logprobs, no_speech_probs = decoding.main_loop(features, row_limit=limit, temperature=per_call)
@@ -162,13 +178,15 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
                               row_limit=limit.clone(), windows=state['windows_host'], languages=list(state['languages']),
                               language_tokens=None if state['tokens'] is None else list(state['tokens']),
                               detected=dict(state['detected']) if new_round else {}, results=results,
+                              prompts=None if prompts is None else [list(p) for p in prompts],
                               n_states=len(decoding._state), n_graphs=len(st['graphs'])))
         return results
 
     segments = longform.transcribe_batched(
         decode_call, [int(c) for c in content_frames], n_rows, window=W, timestamp_begin=tk.timestamp_begin,
         temperatures=temperatures, compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
-        no_speech_threshold=no_speech_threshold, decode_text=tk.decode)
+        no_speech_threshold=no_speech_threshold, decode_text=tk.decode,
+        **(dict(condition_on_previous_text=bool(condition_on_previous_text), initial_prompt=initial_prompt) if prompted else {}))
     out = []
     for f in range(n_files):
         text = tk.decode([t for s in segments[f] for t in s['tokens']]).strip()
@@ -208,6 +226,9 @@ def parse_arguments(argv=None):
                         help='the fallback ladder (default: 0 0.2 0.4 0.6 0.8 1)')
     parser.add_argument('--no_fallback', default=False, action='store_true', help='decode every window once, at the first temperature')
     parser.add_argument('--rows', type=int, default=None, help='rows of a decoder call (default: min(files, what fits))')
+    parser.add_argument('--condition_on_previous_text', default=False, action='store_true',
+                        help="decode every window with the file's text so far as its prompt (upstream's default; off here)")
+    parser.add_argument('--initial_prompt', type=str, default=None, help="text in front of every file's first window: names, spelling, style")
     return parser.parse_args(argv)
 
 
@@ -216,9 +237,11 @@ def main(args) -> List[dict]:
     torch.cuda.set_device(0)
     engine_dir = Path(args.engine_dir)
     encoding = WhisperEncoding(engine_dir)
-    decoding = WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language))
+    prompted = bool(args.condition_on_previous_text or args.initial_prompt)
+    decoding = WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language), row_prompts=prompted)
     temperatures = tuple(args.temperature[:1] if args.no_fallback else args.temperature)
-    results = transcribe(encoding, decoding, args.input_file, temperatures=temperatures, n_rows=args.rows)
+    results = transcribe(encoding, decoding, args.input_file, temperatures=temperatures, n_rows=args.rows,
+                         condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt)
     for path, result in zip(args.input_file, results):
         if len(results) > 1:
             print(f"{path} ({result['language']})")

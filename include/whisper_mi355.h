@@ -60,7 +60,8 @@ typedef struct wm_dims {
  *   7  (round 5) the decoder workspace needs NO initialisation by the caller any more (the library clears the state it keeps there,
  *      on the stream of the call); a one-launch step that gave up makes the NEXT wm_decoder_step fail (rc 1) until
  *      wm_decode_chain_error has been called; wm_decode_chain_status, wm_debug_occupy
- *   8  (round 6) wm_decoder_io gains `not_alone` (appended): the caller says when other decoder steps may run beside this one          */
+ *   8  (round 6) wm_decoder_io gains `not_alone` (appended): the caller says when other decoder steps may run beside this one
+ *      (still 8, like wm_mel_windows / wm_resample) wm_decoder_io gains `row_start` (appended; NULL = as before); wm_attn_decode_self_rows */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -164,6 +165,19 @@ typedef struct wm_decoder_io {
      * half until the bounded waits give up -- so a step that is not alone always takes a launch per kernel.  0 = the caller issues one
      * decoder step at a time on this device (the reference's own schedule, W/decoding.py:785-821).  */
     int32_t not_alone;
+    /* (appended under ABI 8, like wm_mel_windows / wm_resample: NULL = every row begins at slot 0, the behaviour so far)
+     * RIGHT-ALIGNED ROWS: device int32 [batch].  Utterance b's sequence begins at slot row_start[b] of its token row and of its KV
+     * cache; the slots before it are pad (any valid token id).  All rows of the call still share n_past, n_new and the step counter --
+     * only the front of a row moves, so rows with start sequences of different lengths (a prompt per row) fit one call:
+     *   - the positional embedding of slot t of utterance b is row t - row_start[b] of the table (pad slots: row 0).  With n_past_dev
+     *     `positional_embedding` is the table's base as ever; without, it is the table's row n_past AND rows 0 .. n_past - 1 must lie
+     *     in front of it (a slice of the whole table: what decoding.py passes);
+     *   - self-attention: utterance b sees the keys of slots [row_start[b], t] only; a query in a pad slot reads nothing and yields
+     *     zeros (its logits are finite and meaningless); K / V rows are appended at slot t as ever.  A row computes exactly what it
+     *     would compute alone, un-padded, with n_past - row_start[b] cached tokens (csrc/attn_decode.hip states the contract);
+     *   - a call with row_start never takes a one-launch form (as if not_alone were set).
+     * wm_decoder_step only: wm_decoder_step_multi and wm_decoder_step_tap refuse it (rc 1).                                          */
+    const int32_t* row_start;
 } wm_decoder_io;
 size_t wm_decoder_workspace_bytes(const wm_engine* e, int batch, int n_new);
 int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t stream);
@@ -538,6 +552,11 @@ int wm_attn_decode_cross_i8(const float* q, int B, int L, int H, int Tk, const v
 int wm_attn_decode_self(const float* qkv, int B, int L, int T, int H, const void* past, int past_cap,
                         void* present, int present_cap, int int8_kv, float kv_scale, void* out,
                         wm_stream_t stream);
+/* The same in place (past == present == cache, capacity cap) with right-aligned rows and / or a live-row list, as wm_decoder_step
+ * launches it: row_start int32 [B] or NULL (wm_decoder_io::row_start), live_rows int32 [1 + B] or NULL (wm_decoder_io::live_rows:
+ * rows not listed are neither read nor written).  L <= 4.                                                                          */
+int wm_attn_decode_self_rows(const float* qkv, int B, int L, int T, int H, void* cache, int cap, int int8_kv, float kv_scale,
+                             void* out, const int32_t* row_start, const int32_t* live_rows, wm_stream_t stream);
 /* q = sat_s8(rne(x * inv_scale)) (quantizeTensorPlugin / attention.py:340-348). */
 int wm_quantize_i8(const void* x, void* q, int64_t n, float inv_scale, wm_stream_t stream);
 
