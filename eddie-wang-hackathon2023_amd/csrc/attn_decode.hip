@@ -573,7 +573,7 @@ constexpr int CROSS_MAX_SPLIT = 16;                   // key-range splits the me
 // The load instructions stay where they are -- the software pipeline above depends on an unconditional stream -- but a wave
 // instruction whose 8 rows ALL weigh zero (for every token of the call) fetches the item's first 8 V rows instead, which the
 // workgroup has just read (an L2 hit): the data is multiplied by 0 either way.  Bit-identical outputs by construction (tests:
-// test_cross_attention_v_skip_*); the first block of V rows is requested before the softmax and is never skipped.  With random
+// test_cross_attention_v_skip_*, tests/test_gpu_attn_decode_contract.py); the first block of V rows is requested before the softmax and is never skipped.  With random
 // weights (diffuse attention) nothing underflows and nothing is skipped: the bench headline cannot show this, a peaked
 // synthetic fixture and FETCH_SIZE do (profiles/r4*_pmc_vskip*).
 template <int L, bool I8 = false, int UNR_ = 0, bool SKIP = false>

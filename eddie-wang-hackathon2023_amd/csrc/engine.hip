@@ -1415,6 +1415,64 @@ int wm_row_finish(const wm_row_finish_io* io, wm_stream_t stream) {
     return launch_row_finish(p, (hipStream_t)stream);
 }
 
+// the decode attention kernels as the decoder engine calls them (tests/test_gpu_attn_decode_contract.py): what the kernels assume of
+// their arguments is checked here, the launchers' own checks follow
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int wm_attn_self_ex(const wm_attn_self_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io && io->part && io->present && io->out, "wm_attn_self_ex: null argument");
+    WM_REQUIRE(io->B >= 1 && io->H >= 1 && io->L >= 1 && io->T >= 0, "wm_attn_self_ex: bad B/L/T/H (%d, %d, %d, %d)", io->B, io->L, io->T, io->H);
+    const int C = io->H * 64;
+    WM_REQUIRE(io->ksplit >= 1, "wm_attn_self_ex: ksplit=%d must be >= 1", io->ksplit);
+    WM_REQUIRE(io->ldp % 4 == 0 && io->ldp >= 3 * C, "wm_attn_self_ex: ldp=%d must be a multiple of 4, >= 3 * H * 64 = %d", io->ldp, 3 * C);
+    WM_REQUIRE(io->part_sstride >= 0 && io->part_sstride % 4 == 0 && (io->part_sstride == 0 || io->part_sstride >= (int64_t)io->B * io->L * io->ldp),
+               "wm_attn_self_ex: part_sstride must be 0 or a multiple of 4, >= B * L * ldp");
+    WM_REQUIRE(aligned16(io->part) && aligned16(io->bias), "wm_attn_self_ex: part and bias must be 16-byte aligned");
+    WM_REQUIRE(io->ldo >= C, "wm_attn_self_ex: ldo=%d < H * 64 = %d", io->ldo, C);
+    WM_REQUIRE(io->present_cap >= 1 && io->present_bstride >= (int64_t)2 * C * io->present_cap && io->present_bstride % 16 == 0,
+               "wm_attn_self_ex: present_bstride must be a multiple of 16, >= 2 * H * present_cap * 64");
+    WM_REQUIRE(aligned16(io->present) && aligned16(io->past), "wm_attn_self_ex: past and present must be 16-byte aligned");
+    if (io->past) {
+        WM_REQUIRE(io->past_cap >= 1 && io->past_cap >= io->T, "wm_attn_self_ex: past capacity %d < T=%d", io->past_cap, io->T);
+        WM_REQUIRE(io->past_bstride >= (int64_t)2 * C * io->past_cap && io->past_bstride % 16 == 0,
+                   "wm_attn_self_ex: past_bstride must be a multiple of 16, >= 2 * H * past_cap * 64");
+        WM_REQUIRE(io->past != io->present || (io->past_cap == io->present_cap && io->past_bstride == io->present_bstride),
+                   "wm_attn_self_ex: past == present (in place) needs the same capacity and stride");
+    }
+    AttnSelfParams p{};
+    p.part = io->part; p.ksplit = io->ksplit; p.ldp = io->ldp; p.part_sstride = (long)io->part_sstride; p.bias = (const h16*)io->bias;
+    p.B = io->B; p.L = io->L; p.T = io->T; p.H = io->H;
+    p.present = io->present; p.present_cap = io->present_cap; p.present_bstride = (long)io->present_bstride;
+    if (io->past) { p.past = io->past; p.past_cap = io->past_cap; p.past_bstride = (long)io->past_bstride; }
+    else { p.past = p.present; p.past_cap = p.present_cap; p.past_bstride = p.present_bstride; }      // (as the engine at T = 0)
+    p.int8_kv = io->int8_kv ? 1 : 0; p.kv_scale = io->kv_scale; p.amax = io->amax; p.t_dev = io->t_dev;
+    p.out = (h16*)io->out; p.ldo = io->ldo; p.live = io->live; p.row_start = io->row_start; p.waves = io->waves;
+    return launch_attn_self(p, (hipStream_t)stream);
+}
+
+int wm_attn_cross_ex(const wm_attn_cross_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io && io->part && io->kv && io->out, "wm_attn_cross_ex: null argument");
+    WM_REQUIRE(io->B >= 1 && io->H >= 1 && io->L >= 1 && io->Tk >= 1, "wm_attn_cross_ex: bad B/L/H/Tk (%d, %d, %d, %d)", io->B, io->L, io->H, io->Tk);
+    const int C = io->H * 64;
+    WM_REQUIRE(io->ksplit >= 1, "wm_attn_cross_ex: ksplit=%d must be >= 1", io->ksplit);
+    WM_REQUIRE(io->ldp % 4 == 0 && io->ldp >= C, "wm_attn_cross_ex: ldp=%d must be a multiple of 4, >= H * 64 = %d", io->ldp, C);
+    WM_REQUIRE(io->part_sstride >= 0 && io->part_sstride % 4 == 0 && (io->part_sstride == 0 || io->part_sstride >= (int64_t)io->B * io->L * io->ldp),
+               "wm_attn_cross_ex: part_sstride must be 0 or a multiple of 4, >= B * L * ldp");
+    WM_REQUIRE(aligned16(io->part) && aligned16(io->bias) && aligned16(io->kv), "wm_attn_cross_ex: part, bias and kv must be 16-byte aligned");
+    WM_REQUIRE(io->ldo >= C, "wm_attn_cross_ex: ldo=%d < H * 64 = %d", io->ldo, C);
+    WM_REQUIRE(io->kv_bstride >= (int64_t)2 * C * io->Tk && io->kv_bstride % 16 == 0,
+               "wm_attn_cross_ex: kv_bstride must be a multiple of 16, >= 2 * H * Tk * 64");
+    WM_REQUIRE(io->kv_q8_scale >= 0.f, "wm_attn_cross_ex: kv_q8_scale must not be negative");
+    WM_REQUIRE(io->nsplit >= 1 && (io->nsplit == 1 || io->ws), "wm_attn_cross_ex: nsplit=%d needs a workspace", io->nsplit);
+    AttnCrossParams p{};
+    p.part = io->part; p.ksplit = io->ksplit; p.ldp = io->ldp; p.part_sstride = (long)io->part_sstride; p.bias = (const h16*)io->bias;
+    p.B = io->B; p.L = io->L; p.H = io->H; p.Tk = io->Tk; p.kv = (const h16*)io->kv; p.kv_bstride = (long)io->kv_bstride;
+    p.kv_q8_scale = io->kv_q8_scale;
+    p.out = (h16*)io->out; p.ldo = io->ldo; p.nsplit = io->nsplit; p.ws = io->ws; p.live = io->live;
+    p.skip_zero_rows = io->skip_zero_rows ? 1 : 0;
+    return launch_attn_cross(p, (hipStream_t)stream);
+}
+
 int wm_embed(const int32_t* tokens, int tokens_ld, int M, int L, const void* emb_tiles, int C, const void* pos,
              void* x, int ldx, int n_vocab, const int32_t* t_dev, uint32_t* generation, wm_stream_t stream) {
     WM_REQUIRE(tokens && emb_tiles && pos && x, "wm_embed: null argument");

@@ -83,6 +83,7 @@ EXPORTS = (
     "wm_gemm_ex", "wm_row_finish", "wm_embed", "wm_mel_transpose_pad", "wm_zero_pad_rows",
     "wm_decoder_step_tap", "wm_align_workspace_bytes", "wm_align", "wm_dtw_workspace_bytes", "wm_dtw",
     "wm_mel_windows", "wm_resample", "wm_attn_decode_self_rows",
+    "wm_attn_self_ex", "wm_attn_cross_ex",
 )
 
 
@@ -233,6 +234,40 @@ class WmRowFinishIO(C.Structure):
     ]
 
 
+class WmAttnSelfIO(C.Structure):
+    """wm_attn_self_io (include/whisper_mi355.h): the decode self-attention with every field the decoder engine sets (tests)."""
+    _fields_ = [
+        ("part", C.c_void_p), ("ksplit", C.c_int32), ("ldp", C.c_int32), ("part_sstride", C.c_int64),
+        ("bias", C.c_void_p),
+        ("B", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("H", C.c_int32),
+        ("past", C.c_void_p), ("past_bstride", C.c_int64), ("past_cap", C.c_int32),
+        ("present", C.c_void_p), ("present_bstride", C.c_int64), ("present_cap", C.c_int32),
+        ("int8_kv", C.c_int32), ("kv_scale", C.c_float),
+        ("amax", C.c_void_p),
+        ("t_dev", C.c_void_p),
+        ("out", C.c_void_p), ("ldo", C.c_int32),
+        ("live", C.c_void_p),
+        ("row_start", C.c_void_p),
+        ("waves", C.c_int32),
+    ]
+
+
+class WmAttnCrossIO(C.Structure):
+    """wm_attn_cross_io (include/whisper_mi355.h): the decode cross-attention with every field the decoder engine sets (tests)."""
+    _fields_ = [
+        ("part", C.c_void_p), ("ksplit", C.c_int32), ("ldp", C.c_int32), ("part_sstride", C.c_int64),
+        ("bias", C.c_void_p),
+        ("B", C.c_int32), ("L", C.c_int32), ("H", C.c_int32), ("Tk", C.c_int32),
+        ("kv", C.c_void_p), ("kv_bstride", C.c_int64),
+        ("kv_q8_scale", C.c_float),
+        ("out", C.c_void_p), ("ldo", C.c_int32),
+        ("nsplit", C.c_int32),
+        ("ws", C.c_void_p),
+        ("live", C.c_void_p),
+        ("skip_zero_rows", C.c_int32),
+    ]
+
+
 class WmTapIO(C.Structure):
     """wm_tap_io (include/whisper_mi355.h): where wm_decoder_step_tap writes the cross-attention queries."""
     _fields_ = [("q_tape", C.c_void_p), ("capacity", C.c_int32), ("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32)]
@@ -339,6 +374,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_debug_timeline.argtypes = [vp, i32]
     lib.wm_gemm_ex.argtypes = [C.POINTER(WmGemmIO), vp]
     lib.wm_row_finish.argtypes = [C.POINTER(WmRowFinishIO), vp]
+    lib.wm_attn_self_ex.argtypes = [C.POINTER(WmAttnSelfIO), vp]
+    lib.wm_attn_cross_ex.argtypes = [C.POINTER(WmAttnCrossIO), vp]
     lib.wm_embed.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp]
     lib.wm_mel_transpose_pad.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.wm_zero_pad_rows.argtypes = [vp, i32, i32, i32, vp]

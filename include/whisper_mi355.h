@@ -61,7 +61,8 @@ typedef struct wm_dims {
  *      on the stream of the call); a one-launch step that gave up makes the NEXT wm_decoder_step fail (rc 1) until
  *      wm_decode_chain_error has been called; wm_decode_chain_status, wm_debug_occupy
  *   8  (round 6) wm_decoder_io gains `not_alone` (appended): the caller says when other decoder steps may run beside this one
- *      (still 8, like wm_mel_windows / wm_resample) wm_decoder_io gains `row_start` (appended; NULL = as before); wm_attn_decode_self_rows */
+ *      (still 8, like wm_mel_windows / wm_resample) wm_decoder_io gains `row_start` (appended; NULL = as before); wm_attn_decode_self_rows
+ *      (still 8: test-only entries, no existing struct or signature changed) wm_attn_self_ex, wm_attn_cross_ex */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -395,6 +396,56 @@ typedef struct wm_row_finish_io {
     void* out; int32_t ldo;
 } wm_row_finish_io;
 int wm_row_finish(const wm_row_finish_io* io, wm_stream_t stream);
+/* The decode attention kernels (csrc/attn_decode.hip) with every field of AttnSelfParams / AttnCrossParams that the decoder engine
+ * sets, reachable alone (tests/test_gpu_attn_decode_contract.py; wm_attn_decode_self / _self_rows / _cross / _cross_i8 below fix
+ * ksplit = 1, no bias, dense strides, ldo = C, a host T).  Not used by the product path.
+ * Both: q (and k, v) rows arrive as fp32 split-K slabs part[ksplit][B * L][ldp], slabs part_sstride elements apart (0: B * L * ldp);
+ *   row = fp16(sum_s part[s][row][:] + bias) (bias fp16, may be NULL); live (optional, DEVICE int32 [1 + B]): count, then the rows to
+ *   process -- the other rows' outputs, caches and workspace blocks are not touched.
+ * wm_attn_self_ex: slab columns q | k | v (3 * H * 64), bias [3 * H * 64]; the k / v rows are appended at slots T .. T + L - 1 of
+ *   present [B][2][H][present_cap][64] (fp16, or int8 codes sat_s8(rne(x * (1 / kv_scale))) with int8_kv), utterances present_bstride
+ *   elements apart; past (NULL: present) holds the T cached slots, and is copied forward when it is another buffer; t_dev (optional,
+ *   DEVICE int32): T is read from it on the device (the host T must still fit present_cap); amax (optional, DEVICE fp32): atomic
+ *   running maximum of |q|, |k|, |v| (the fp16 rows, before the d^-0.25 scale) over the rows processed; row_start (optional, DEVICE
+ *   int32 [B]): right-aligned rows, as wm_attn_decode_self_rows; waves 0 / 1: one wave per (utterance, head), 4: the workgroup form
+ *   -- passed straight through (wm_set_self_attn_waves is not consulted).
+ * wm_attn_cross_ex: slab columns q (H * 64), bias [H * 64]; kv [B][2][H][Tk][64] fp16, or int8 codes with value code * kv_q8_scale
+ *   when kv_q8_scale > 0, utterances kv_bstride elements apart; nsplit > 1 splits the key range and needs ws, fp32
+ *   [B * H * nsplit * L * 66], indexed by the ORIGINAL row with a live list; skip_zero_rows is passed straight through
+ *   (wm_set_cross_v_skip is not consulted).
+ * Refused (rc 1, nothing launched): a null part / present / kv / out; B, H < 1, T < 0; ksplit < 1; ldp or part_sstride not a multiple
+ *   of 4, ldp < 3 * H * 64 (self) / H * 64 (cross), 0 < part_sstride < B * L * ldp; part, bias, past, present, kv not 16-byte
+ *   aligned; ldo < H * 64; past_bstride / present_bstride / kv_bstride below one utterance's extent or not a multiple of 16;
+ *   past_cap < T; past == present with another capacity or stride; kv_q8_scale < 0; nsplit > 1 without ws; and whatever the
+ *   launchers refuse (L outside 1 .. 4, T + L > 512 or > present_cap, Tk outside 1 .. 1536, nsplit outside 1 .. 16, waves). */
+typedef struct wm_attn_self_io {
+    const float* part; int32_t ksplit, ldp; int64_t part_sstride;
+    const void* bias;
+    int32_t B, L, T, H;
+    const void* past; int64_t past_bstride; int32_t past_cap;
+    void* present; int64_t present_bstride; int32_t present_cap;
+    int32_t int8_kv; float kv_scale;
+    float* amax;
+    const int32_t* t_dev;
+    void* out; int32_t ldo;
+    const int32_t* live;
+    const int32_t* row_start;
+    int32_t waves;
+} wm_attn_self_io;
+int wm_attn_self_ex(const wm_attn_self_io* io, wm_stream_t stream);
+typedef struct wm_attn_cross_io {
+    const float* part; int32_t ksplit, ldp; int64_t part_sstride;
+    const void* bias;
+    int32_t B, L, H, Tk;
+    const void* kv; int64_t kv_bstride;
+    float kv_q8_scale;
+    void* out; int32_t ldo;
+    int32_t nsplit;
+    float* ws;
+    const int32_t* live;
+    int32_t skip_zero_rows;
+} wm_attn_cross_io;
+int wm_attn_cross_ex(const wm_attn_cross_io* io, wm_stream_t stream);
 /* x[r] = fp16(E[token of row r] + pos[r % L + T]), r < M = B * L; token of row r = tokens[(r / L) * tokens_ld + r % L + T];
  * T = *t_dev when given, else 0.  emb_tiles: the fp16 embedding in tile-linear layout (weight.py: tile_linear), C a multiple
  * of 32; token ids are clamped to [0, n_vocab).  generation (optional): incremented once per call. */
@@ -527,7 +578,8 @@ int wm_decode_chain_status(wm_chain_status* out);
 int wm_debug_occupy(int n_workgroups, size_t lds_bytes, int64_t microseconds, wm_stream_t stream);
 /* Exact V-row skipping in the decode cross-attention (fp16 K/V, single-pass form): a key whose softmax probability rounds to
  * fp16 zero contributes exactly nothing to P.V, so the wave instructions whose 8 rows all weigh zero do not fetch them from
- * HBM (they re-read 8 rows the workgroup has just used).  Outputs are bit-identical with it on or off for finite V.  1 = on
+ * HBM (they re-read 8 rows the workgroup has just used).  Outputs are bit-identical with it on or off for finite V
+ * (tests/test_gpu_round4.py::test_cross_attention_v_skip_*, tests/test_gpu_attn_decode_contract.py).  1 = on
  * (default), 0 = off, < 0 = the default.  Returns the previous value.  Captured graphs keep the form they were captured with. */
 int wm_set_cross_v_skip(int on);
 /* Lab knobs (environment variables such as WM_CROSS_NSPLIT, WM_ROWS_MIN, WM_KSPLIT_CAP: DESIGN.md, scripts/README.md) change a

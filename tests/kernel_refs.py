@@ -1,5 +1,6 @@
-"""Plain restatements of what the MFMA GEMM epilogue and the row kernels compute, for the kernel-level parity tests
-(tests/test_gpu_gemm_epilogue.py, tests/test_gpu_row_kernels.py), and the case lists those tests run.
+"""Plain restatements of what the MFMA GEMM epilogue, the row kernels and the decode attention kernels compute, for the kernel-level
+parity tests (tests/test_gpu_gemm_epilogue.py, tests/test_gpu_row_kernels.py, tests/test_gpu_attn_decode_contract.py), and the case
+lists those tests run.
 
 Everything here is torch in float64 over the fp16-rounded inputs, with the kernels' rounding points and nothing of their structure:
 no tiles, no lanes, no summation order.  A rounding point is `r16`: the kernels hold an fp32 value there and convert it to fp16, so
@@ -159,6 +160,102 @@ def exact_grid(r, shape, steps, step):
     return (r.integers(-steps, steps + 1, size=shape) * step).astype(np.float32)
 
 
+# ---------------------------------------------------------------------------------------------- decode attention
+def qkv_rows_ref(part, bias=None):
+    """The prologue of the decode attention kernels: fp16(sum_s part[s] + bias).  part [ksplit, M, N] fp32, bias [N] fp16 or None."""
+    y = part.to(torch.float64).sum(0)
+    if bias is not None:
+        y = y + bias.to(torch.float64)[None, :]
+    return r16(y)
+
+
+def attn_decode_ref(q, K, V, mask=None, k_exact=False):
+    """The contract at the top of csrc/attn_decode.hip.  q [B, H, L, 64], K / V [B, H, Tk, 64] (fp16 values, or the exact products
+    code * t of the int8 cross mode), mask [L, Tk] additive (0 | -inf) or None.  qh = fp16(q s), kh = fp16(k s) with s = 64^-0.25 as
+    fp32 (k_exact: kh = k s, not rounded); scores fp16(qh . kh); softmax in float64, probabilities through fp16; out = fp16(P . V).
+    Returns float64 [B, H, L, 64] holding fp16 values."""
+    s = float(np.float32(QK_SCALE))
+    qh = r16(q.to(torch.float64) * s)
+    kh = K.to(torch.float64) * s
+    if not k_exact:
+        kh = r16(kh)
+    sc = r16(qh @ kh.transpose(-1, -2))
+    if mask is not None:
+        sc = sc + mask.to(torch.float64)
+    return r16(r16(torch.softmax(sc, dim=-1)) @ V.to(torch.float64))
+
+
+def self_cache_codes(x, t):
+    """The int8 self-attention cache: sat_s8(rne(x * (1 / t))), 1 / t formed in fp32."""
+    return quant_codes(x, np.float32(1.0) / np.float32(t))
+
+
+def self_cache_values(codes, t):
+    """What a cached code is worth as a past key / value: fp16(code * t)."""
+    return r16(codes.to(torch.float64) * float(np.float32(t)))
+
+
+def cross_i8_values(codes, t):
+    """int8 cross K/V: exactly code * t (no rounding of the dequantised tensor)."""
+    return codes.to(torch.float64) * float(np.float32(t))
+
+
+def split_heads(rows, B, L, H):
+    """[B * L, H * 64] -> [B, H, L, 64]."""
+    return rows.reshape(B, L, H, 64).permute(0, 2, 1, 3)
+
+
+def merge_heads(x):
+    """[B, H, L, 64] -> [B * L, H * 64]."""
+    B, H, L, _ = x.shape
+    return x.permute(0, 2, 1, 3).reshape(B * L, H * 64)
+
+
+def attn_self_ref(rows, past_vals, B, L, T, H):
+    """Decode self-attention on the fp16 rows [B * L, 3 * H * 64] (q | k | v) over past_vals [B, 2, H, T, 64] (the VALUES of the cached
+    slots: fp16, or self_cache_values of the codes) followed by the call's own k / v, causal inside the call.  -> [B * L, H * 64]."""
+    C = H * 64
+    q, k, v = (split_heads(rows[:, i * C:(i + 1) * C], B, L, H) for i in range(3))
+    K = torch.cat([past_vals[:, 0].to(torch.float64), k], dim=2)
+    V = torch.cat([past_vals[:, 1].to(torch.float64), v], dim=2)
+    mask = torch.zeros(L, T + L, dtype=torch.float64)
+    mask[:, T:] = torch.full((L, L), float("-inf"), dtype=torch.float64).triu_(1)
+    return merge_heads(attn_decode_ref(q, K, V, mask))
+
+
+def amax_ref(rows):
+    """The calibration hook: max |q|, |k|, |v| of the fp16 rows the launch processes (before the d^-0.25 scale), as fp32."""
+    return np.float32(float(rows.abs().max()))
+
+
+def ordinary_slabs(r, ksplit, M, N):
+    """Random fp32 slabs off any grid, scaled by 1 / sqrt(ksplit), and a small fp16 bias: fp16(sum + bias) has about unit variance, like
+    the inputs of tests/test_gpu_kernels.py::test_attn_decode_* whose bounds the ordinary-sum tests use.  -> part [ksplit, M, N], bias [N]"""
+    part = (r.standard_normal((ksplit, M, N)) / math.sqrt(ksplit)).astype(np.float32)
+    bias = (r.standard_normal(N) * 0.1).astype(np.float16)
+    return torch.from_numpy(part), torch.from_numpy(bias)
+
+
+def boundary_excused(part, bias=None):
+    """Elements of fp16(sum_s part[s] + bias) whose fp16 rounding may legitimately depend on the ORDER of the fp32 additions: the
+    float64 sum lies within one fp32 ulp of an fp16 rounding boundary (a midpoint of two neighbouring fp16 values).  The ulp is taken
+    at A = sum_s |part[s]| + |bias|, which bounds every partial sum in every order: each fp32 addition is off by at most half an ulp of
+    its own result, and no result exceeds A.  Computed from the float64 sum alone.  -> bool [M, N]."""
+    p64 = part.to(torch.float64)
+    y = p64.sum(0)
+    A = p64.abs().sum(0)
+    if bias is not None:
+        y = y + bias.to(torch.float64)[None, :]
+        A = A + bias.to(torch.float64).abs()[None, :]
+    h = y.to(torch.float32).to(torch.float16)
+    inf = torch.tensor(float("inf"), dtype=torch.float16)
+    up, dn = torch.nextafter(h, inf).to(torch.float64), torch.nextafter(h, -inf).to(torch.float64)
+    h = h.to(torch.float64)
+    dist = torch.minimum((y - (h + up) / 2).abs(), (y - (h + dn) / 2).abs())
+    ulp = torch.exp2(torch.floor(torch.log2(A.clamp_min(2.0 ** -126))) - 23)
+    return dist <= ulp
+
+
 # ---------------------------------------------------------------------------------------------- dispatch, restated
 SMALL_TILES_DEFAULT, TINY_TILES = 150, 160
 FORMS = ("f16<8,256>", "f16<8,128>", "f16<4,128>", "f16<2,128>")      # gemm_f16_kernel<NWAVE, BN>: 256x256, 256x128, 128x128, 64x128 tiles
@@ -241,3 +338,103 @@ TILE_ORDER_SHAPES = [(256 * 37 - 100, 1280, 128), (1024, 1280, 128), (256 * 13, 
 TILE_ROWS = [1, 2, 3, 8]
 CU_BUDGET_SHAPES = [(6000, 1280, 1280), (12000, 2560, 1280)]
 CU_BUDGETS = [1, 8, 20, 64, 100]
+
+
+# ---------------------------------------------------------------------------------------------- decode attention: dispatch, cases
+ATTN_KSPLITS = [1, 2, 3, 4, 5, 7, 8]              # every ksplit % 4, odd and even: full rounds of four, half rounds, scalar tails
+CROSS_VARIANTS = ("fp16", "fp16+SKIP", "int8")
+SELF_MAX_T, CROSS_MAX_KEYS, CROSS_MAX_SPLIT = 512, 1536, 16
+
+
+def self_dispatch(int8_kv, row_start, waves):
+    """launch_attn_self (csrc/attn_decode.hip): (I8, RS, form) of the kernel template a call reaches."""
+    return (bool(int8_kv), bool(row_start), "workgroup" if waves == 4 else "one-wave")
+
+
+def every_self_instantiation():
+    return {(i8, rs, form) for i8 in (False, True) for rs in (False, True) for form in ("one-wave", "workgroup")}
+
+
+def cross_per_split(Tk, nsplit):
+    """Keys per split: the share rounded up to a multiple of 8 (attn_cross_kernel)."""
+    return (((Tk + nsplit - 1) // nsplit) + 7) & ~7
+
+
+def cross_empty_splits(Tk, nsplit):
+    per = cross_per_split(Tk, nsplit)
+    return sum(1 for sp in range(nsplit) if min(Tk, sp * per + per) - sp * per <= 0)
+
+
+def cross_uq(L, int8):
+    """Slabs per round of attn_cross_kernel's q prologue (even, at least 2)."""
+    qv = 4 if int8 else 2
+    return max(8 // (L * qv), 2)
+
+
+def cross_dispatch(L, int8, skip, nsplit, H, B, n_cu):
+    """launch_attn_cross: the kernel template (L, variant), the launch form and grid, and whether the combine kernel runs.  The grid is
+    sized from B (not from a live-row list): one workgroup per (head, row, split) item, or -- from four items per CU -- at most two
+    workgroups per CU, every one with the same number of items."""
+    variant = "int8" if int8 else ("fp16+SKIP" if skip and nsplit == 1 else "fp16")
+    n_items = H * B * nsplit
+    wgs = 0
+    if n_items >= 4 * n_cu:
+        per = (n_items + 2 * n_cu - 1) // (2 * n_cu)
+        wgs = (n_items + per - 1) // per
+    grid = wgs if 0 < wgs < n_items else n_items
+    return {"kernel": (L, variant), "launch": "persistent" if grid < n_items else "per-item", "grid": grid, "items": n_items,
+            "combine": nsplit > 1}
+
+
+def every_cross_instantiation():
+    return {(L, v) for L in (1, 2, 3, 4) for v in CROSS_VARIANTS}
+
+
+def persistent_batch(n_cu, H=2, nsplit=8):
+    """The smallest B whose H * B * nsplit items make the launch persistent on a device of n_cu CUs."""
+    return (4 * n_cu + H * nsplit - 1) // (H * nsplit)
+
+
+def _self_exact_cases():
+    """(ksplit, int8_kv, waves, rs, L, T, bias, strided, ldp_pad, ldo_pad, inplace): every ksplit x cache type x wave form x T; the
+    other axes cycle with co-prime periods so that every value of every axis occurs (tests/test_kernel_refs_cpu.py counts them)."""
+    cases, n = [], 0
+    for ks in ATTN_KSPLITS:
+        for i8 in (0, 1):
+            for waves in (1, 4):
+                for T in (0, 5, 64, 130):
+                    L = (1, 3, 4)[n % 3]
+                    cases.append((ks, i8, waves, 0, L, T, (n // 3) % 2 == 0, (n // 5) % 2 == 1, 4 * ((n // 2) % 2), 8 * ((n // 7) % 2),
+                                  (n // 4 + n) % 2 == 0))
+                    n += 1
+    for ks in (4, 7):                              # right-aligned rows through the new entry (in place, as the decode loop runs them)
+        for i8 in (0, 1):
+            for waves in (1, 4):
+                cases.append((ks, i8, waves, 1, 3, 5, True, True, 4, 8, True))
+    return cases
+
+
+def _cross_exact_cases():
+    """(ksplit, L, variant, nsplit, Tk, H, bias): every ksplit at every L and variant (each slabs-per-round value meets a full round, a
+    half round and a tail); the V-skip form exists for the single pass only."""
+    cases, n = [], 0
+    for ks in ATTN_KSPLITS:
+        for L in (1, 2, 3, 4):
+            for v in CROSS_VARIANTS:
+                nsplit = 1 if v == "fp16+SKIP" else (1, 3)[(n // 3) % 2]
+                cases.append((ks, L, v, nsplit, (100, 333)[(n // 2 + n // 5) % 2], 1 + n % 3, n % 5 != 4))
+                n += 1
+    return cases
+
+
+SELF_EXACT_CASES = _self_exact_cases()
+CROSS_EXACT_CASES = _cross_exact_cases()
+SELF_ROW_START = [3, 6]                            # B = 2, T = 5, L = 3: pad slots inside the cache | the cache all pad and one pad token
+# (Tk, nsplit, H): key ranges shorter than a load instruction's 8 rows, empty splits (5 of 8, 3 of 16), the maximum key count
+CROSS_EDGE_CASES = [(1, 1, 2), (5, 1, 3), (7, 1, 2), (8, 1, 1), (9, 1, 2), (20, 8, 2), (100, 16, 3), (1536, 1, 1), (1536, 16, 1)]
+CROSS_LIVE_CASES = [(L, nsplit, v) for L in (1, 3) for nsplit in (1, 4) for v in ("fp16", "int8")]      # B = 4, live = [2; 3, 1]
+# ordinary (order-dependent) sums: (ksplit, int8_kv, waves, L, T) and (ksplit, L, variant, nsplit, Tk)
+SELF_SUM_CASES = [(ks, i8, waves, L, T) for ks in (4, 7) for i8 in (0, 1) for waves, L, T in ((1, 3, 5), (4, 1, 130))]
+CROSS_SUM_CASES = [(ks, L, v, ns, Tk) for ks in (4, 7) for L, v, ns, Tk in ((1, "fp16", 1, 100), (4, "fp16", 3, 333), (3, "int8", 1, 333),
+                                                                            (2, "fp16+SKIP", 1, 100), (1, "int8", 3, 100))]
+SUM_SEED = 20240                                   # tests/test_kernel_refs_cpu.py: the excused share of every case at this seed

@@ -232,3 +232,161 @@ def test_tile_order_shapes_take_every_branch():
                 if R == 1:
                     assert order == plain                      # tile_rows = 1 is the plain row-major order
     assert all(seen.values()), seen
+
+
+# ---------------------------------------------------------------------------------------------- decode attention
+def _oracle(H, Tk):
+    from oracle.whisper_oracle import Dims, OracleConfig, OracleModel
+    return OracleModel(Dims(80, Tk, H * 64, H, 0, 8, 512, H * 64, H, 0), {}, OracleConfig(act="float16"))
+
+
+ATTEND_SHAPES = [(2, 1, 2, 100), (2, 3, 2, 37), (1, 4, 3, 333), (3, 2, 1, 8)]          # (B, L, H, Tk)
+
+
+def test_attn_decode_ref_agrees_with_the_oracle():
+    """attn_decode_ref (float64 softmax and dot products) against OracleModel._attend (fp32) on four shapes x (no mask | causal over
+    the last L keys) x (k rounded | k_exact): equal after the final fp16 rounding except where a value sits on a rounding boundary.
+    Measured here: 20 of 8704 elements differ (at most 6 of one comparison's 768), by 1.2e-4 at most (one fp16 ulp of the value, or the
+    little more that one SCORE rounded the other way moves an output).  The oracle ALONE is no steadier: with nothing but the order of
+    its keys changed (two permutations per shape) 15 of 8704 of its own outputs change, at most 5 of 768 = 0.65 % -- so the bound is
+    1 % of a comparison's elements, each within 2.5e-4: a quarter of the 1e-3 the kernels are held to against either reference."""
+    total = differ = 0
+    for seed, (B, L, H, Tk) in enumerate(ATTEND_SHAPES):
+        r = KR.philox(seed)
+        q, k, v = (_t(r.standard_normal((B, n, H * 64)).astype(np.float16)).float() for n in (L, Tk, Tk))
+        heads = lambda x: x.view(B, -1, H, 64).permute(0, 2, 1, 3)                     # noqa: E731
+        m = _oracle(H, Tk)
+        causal = torch.zeros(L, Tk)
+        causal[:, Tk - L:] = torch.full((L, L), float("-inf")).triu_(1)
+        for mask in (None, causal):
+            for k_exact in (False, True):
+                want = m._attend(q, k, v, H, mask, k_exact=k_exact).double()
+                got = KR.merge_heads(KR.attn_decode_ref(heads(q), heads(k), heads(v), mask, k_exact)).reshape(B, L, H * 64)
+                bad = got != want
+                assert float((got - want).abs().max()) <= 2.5e-4, (B, L, H, Tk, k_exact)
+                assert int(bad.sum()) <= 0.01 * want.numel(), (B, L, H, Tk, k_exact, int(bad.sum()))
+                total, differ = total + want.numel(), differ + int(bad.sum())
+    assert differ <= 0.005 * total, (differ, total)
+
+
+@pytest.mark.parametrize("int8_kv", [0, 1])
+def test_attn_self_ref_agrees_with_the_oracle_over_a_cache(int8_kv):
+    """The int8 cache of the reference: self_cache_codes / self_cache_values are kv_quantize / kv_dequantize exactly, and the causal
+    attention over [cached values, this call's k / v] agrees with the oracle as above (measured: 0 and 2 of 768 elements differ)."""
+    from oracle.whisper_oracle import kv_dequantize, kv_quantize
+    B, L, T, H, t = 2, 3, 7, 2, 0.031
+    r = KR.philox(5 + int8_kv)
+    rows = _t(r.standard_normal((B * L, 3 * H * 64)).astype(np.float16))
+    past = _t((r.standard_normal((B, 2, H, T, 64)) * 1.2).astype(np.float16))
+    if int8_kv:
+        codes = KR.self_cache_codes(past, t)
+        assert torch.equal(codes, kv_quantize(past.float(), t))
+        vals = KR.self_cache_values(codes, t)
+        assert torch.equal(vals, kv_dequantize(codes, t, "float16").double())
+        exact = KR.cross_i8_values(codes, t)                                           # code * t in float64: no rounding at all
+        assert torch.equal(exact.float(), codes.float() * float(np.float32(t)))        # ... the oracle's fp32 product is its rounding
+    else:
+        vals = past.double()
+    got = KR.attn_self_ref(rows.double(), vals, B, L, T, H)
+    qkv = rows.float().reshape(B, L, 3, H, 64)
+    full = torch.cat([vals.float(), qkv[:, :, 1:].permute(0, 2, 3, 1, 4)], dim=3)
+    mask = torch.zeros(L, T + L)
+    mask[:, T:] = torch.full((L, L), float("-inf")).triu_(1)
+    k_all, v_all = (full[:, i].permute(0, 2, 1, 3).reshape(B, T + L, H * 64) for i in (0, 1))
+    want = _oracle(H, 8)._attend(qkv[:, :, 0].reshape(B, L, H * 64), k_all, v_all, H, mask).double().reshape(B * L, H * 64)
+    assert float((got - want).abs().max()) <= 2.5e-4
+    assert int((got != want).sum()) <= 0.01 * want.numel()
+
+
+def test_qkv_rows_and_amax_refs():
+    r = KR.philox(9)
+    part = _t(KR.exact_grid(r, (5, 4, 64), 600, 2.0 ** -10))
+    bias = _t(KR.exact_grid(r, (64,), 256, 2.0 ** -10)).half()
+    want = (part.double().sum(0) + bias.double()).half().double()                      # exact on the grid: one rounding
+    assert torch.equal(KR.qkv_rows_ref(part, bias), want)
+    assert torch.equal(KR.qkv_rows_ref(part[:1]), part[0].half().double())
+    assert KR.amax_ref(want) == np.float32(want.abs().max()) and KR.amax_ref(want).dtype == np.float32
+    # a sum that sits exactly on the midpoint of two fp16 values is excused, its neighbours half an fp16 step away are not
+    mid = torch.tensor([[[1.0 + 2.0 ** -11, 1.0 + 2.0 ** -10, 1.0 + 2.0 ** -11 + 2.0 ** -24]]], dtype=torch.float32)
+    assert KR.boundary_excused(mid).tolist() == [[True, False, True]]
+
+
+def test_decode_attention_cases_reach_every_instantiation():
+    """By the launchers' own dispatch (kernel_refs.self_dispatch / cross_dispatch): the exactness lists of
+    tests/test_gpu_attn_decode_contract.py reach all 8 self-attention and all 12 cross-attention kernel templates, with and without the
+    combine kernel, and the two launch forms -- per item at the lists' sizes on any device, persistent for persistent_batch(n_cu)."""
+    self_seen = {}
+    for (ks, i8, waves, rs, *_rest) in KR.SELF_EXACT_CASES:
+        self_seen.setdefault(KR.self_dispatch(i8, rs, waves), set()).add(ks)
+    assert set(self_seen) == KR.every_self_instantiation() and len(self_seen) == 8
+    assert all(ks >= {4, 7} for ks in self_seen.values())
+    assert all(self_seen[(i8, False, f)] == set(KR.ATTN_KSPLITS) for i8 in (False, True) for f in ("one-wave", "workgroup"))
+    cross_seen, combine = {}, set()
+    for n_cu in (64, 256, 304):
+        for (ks, L, v, nsplit, Tk, H, bias) in KR.CROSS_EXACT_CASES:
+            d = KR.cross_dispatch(L, v == "int8", v == "fp16+SKIP", nsplit, H, 2, n_cu)
+            assert d["kernel"] == (L, v) and d["launch"] == "per-item" and d["grid"] == H * 2 * nsplit
+            cross_seen.setdefault(d["kernel"], set()).add(ks)
+            combine.add((v, d["combine"]))
+        B = KR.persistent_batch(n_cu)
+        d = KR.cross_dispatch(1, False, False, 8, 2, B, n_cu)
+        assert d["launch"] == "persistent" and d["grid"] <= 2 * n_cu and d["items"] % d["grid"] == 0 or d["grid"] < d["items"]
+        assert KR.cross_dispatch(1, False, False, 8, 2, B - 1, n_cu)["launch"] == "per-item"
+    assert KR.persistent_batch(256) == 64
+    assert set(cross_seen) == KR.every_cross_instantiation() and len(cross_seen) == 12
+    assert all(ks == set(KR.ATTN_KSPLITS) for ks in cross_seen.values())
+    assert combine == {("fp16", False), ("fp16", True), ("int8", False), ("int8", True), ("fp16+SKIP", False)}
+    # slabs per round of the cross prologue: 4, 2, 2, 2 (fp16) and 2 (int8); every list value meets a full round, a half round, a tail
+    assert [KR.cross_uq(L, False) for L in (1, 2, 3, 4)] == [4, 2, 2, 2] and {KR.cross_uq(L, True) for L in (1, 2, 3, 4)} == {2}
+    for L, v in cross_seen:
+        uq = KR.cross_uq(L, v == "int8")
+        assert {ks % uq for ks in cross_seen[(L, v)]} >= set(range(min(uq, 4))), (L, v)
+    # every value of the other axes of the self list occurs
+    axes = list(zip(*KR.SELF_EXACT_CASES))
+    assert set(axes[4]) == {1, 3, 4} and set(axes[5]) == {0, 5, 64, 130}
+    assert all(set(axes[i]) == {False, True} for i in (6, 7, 10)) and set(axes[8]) == {0, 4} and set(axes[9]) == {0, 8}
+    for ks in KR.ATTN_KSPLITS:                     # ... and every ksplit meets both values of the bias / stride axes, in both wave forms
+        mine = [c for c in KR.SELF_EXACT_CASES if c[0] == ks and not c[3]]
+        assert {c[5] for c in mine} == {0, 5, 64, 130} and {c[4] for c in mine} == {1, 3, 4}
+        for i in (6, 7, 8, 9, 10):
+            assert len({(c[2], c[i]) for c in mine}) == 4, (ks, i)
+    axes = list(zip(*KR.CROSS_EXACT_CASES))
+    assert set(axes[3]) == {1, 3} and set(axes[4]) == {100, 333} and set(axes[5]) == {1, 2, 3} and set(axes[6]) == {False, True}
+    for lst in (KR.SELF_SUM_CASES, KR.CROSS_SUM_CASES):
+        assert {c[0] for c in lst} == {4, 7}
+    assert {KR.self_dispatch(i8, False, w) for (_, i8, w, _, _) in KR.SELF_SUM_CASES} == {c for c in KR.every_self_instantiation() if not c[1]}
+    assert {v for (_, _, v, _, _) in KR.CROSS_SUM_CASES} == set(KR.CROSS_VARIANTS)
+
+
+def test_ksplit_lists_cover_every_remainder():
+    for lst in (KR.ATTN_KSPLITS, sorted({c[0] for c in KR.SELF_EXACT_CASES}), sorted({c[0] for c in KR.CROSS_EXACT_CASES})):
+        assert {ks % 4 for ks in lst} == {0, 1, 2, 3} and any(ks % 2 for ks in lst) and min(lst) == 1
+    assert {c[0] % 4 for c in KR.SELF_SUM_CASES} == {0, 3} and {c[0] % 4 for c in KR.CROSS_SUM_CASES} == {0, 3}
+
+
+def test_split_lists_contain_empty_splits():
+    def empty(Tk, nsplit):
+        per_split = (((Tk + nsplit - 1) // nsplit) + 7) & ~7
+        assert per_split == KR.cross_per_split(Tk, nsplit)
+        n = sum(1 for sp in range(nsplit) if max(0, min(Tk, sp * per_split + per_split) - sp * per_split) == 0)
+        assert n == KR.cross_empty_splits(Tk, nsplit)
+        return n
+    assert empty(20, 8) == 5 and empty(100, 16) == 3 and empty(1536, 16) == 0 and empty(64, 8) == 0
+    edges = {(Tk, ns): empty(Tk, ns) for (Tk, ns, _) in KR.CROSS_EDGE_CASES}
+    assert edges[(20, 8)] == 5 and edges[(100, 16)] == 3
+    assert {Tk for (Tk, ns, _) in KR.CROSS_EDGE_CASES if ns == 1} >= {1, 5, 7, 8, 9, KR.CROSS_MAX_KEYS}
+    assert (KR.CROSS_MAX_KEYS, KR.CROSS_MAX_SPLIT, 1) in KR.CROSS_EDGE_CASES
+    assert all(H == 1 for (Tk, _, H) in KR.CROSS_EDGE_CASES if Tk > 333) and all(H <= 3 for (_, _, H) in KR.CROSS_EDGE_CASES)
+    # the exactness and live-row lists split their keys without an empty split (that is the edge list's business)
+    assert all(empty(Tk, ns) == 0 for (_, _, _, ns, Tk, _, _) in KR.CROSS_EXACT_CASES)
+
+
+def test_ordinary_sum_seed_keeps_the_excused_share_small():
+    """The ordinary-sum GPU tests excuse an appended cache element only where boundary_excused() says the fp32 order may decide its
+    rounding; from the reference alone, at the seed those tests use, that is well under 1 % of every case's elements (measured:
+    0.13 % .. 0.52 %), and the rows have about unit variance (the tolerances of the comparisons rest on O(1) values)."""
+    for (ks, i8, waves, L, T) in KR.SELF_SUM_CASES:
+        part, bias = KR.ordinary_slabs(KR.philox(KR.SUM_SEED + ks), ks, 2 * L, 3 * 128)
+        share = float(KR.boundary_excused(part, bias).double().mean())
+        assert share < 0.01, (ks, L, share)
+        assert 0.9 < float(KR.qkv_rows_ref(part, bias).std()) < 1.1
