@@ -1497,6 +1497,24 @@ int wm_argmax(const void* logits, int64_t row_stride, int batch, int n_vocab, in
     return launch_argmax((const h16*)logits, (long)row_stride, batch, n_vocab, ids, (hipStream_t)stream);
 }
 
+int wm_forced_probs(const void* logits, int batch, int n_pos, int n_vocab, int64_t stride_b, int64_t stride_p, int limit,
+                    const int32_t* next, int next_ld, float* out, int out_ld, wm_stream_t stream) {
+    WM_REQUIRE(logits && next && out, "wm_forced_probs: null argument");
+    WM_REQUIRE(batch >= 1 && n_pos >= 1 && n_vocab >= 1, "wm_forced_probs: batch=%d n_pos=%d n_vocab=%d must be >= 1", batch, n_pos,
+               n_vocab);
+    WM_REQUIRE(limit >= 1 && limit <= n_vocab, "wm_forced_probs: limit=%d must lie in [1, n_vocab=%d]", limit, n_vocab);
+    WM_REQUIRE(stride_p >= n_vocab && stride_b >= (int64_t)(n_pos - 1) * stride_p + n_vocab,
+               "wm_forced_probs: strides (%lld, %lld) let rows of %d logits overlap (n_pos=%d)", (long long)stride_b,
+               (long long)stride_p, n_vocab, n_pos);
+    WM_REQUIRE(next_ld >= n_pos && out_ld >= n_pos, "wm_forced_probs: next_ld=%d / out_ld=%d are below n_pos=%d", next_ld, out_ld, n_pos);
+    WM_REQUIRE((int64_t)batch * n_pos <= 0x7fffffffLL, "wm_forced_probs: batch * n_pos = %lld rows exceed 2^31 - 1",
+               (long long)batch * n_pos);
+    WM_REQUIRE(((uintptr_t)logits & 1) == 0 && ((uintptr_t)next & 3) == 0 && ((uintptr_t)out & 3) == 0,
+               "wm_forced_probs: logits must be 2-byte aligned, next and out 4-byte aligned");
+    return launch_forced_probs((const h16*)logits, (long)stride_b, (long)stride_p, batch, n_pos, limit, next, next_ld, out, out_ld,
+                               (hipStream_t)stream);
+}
+
 int wm_gemm_skinny(const void* A, int lda, int M, int K, const void* Wt, int n_blocks, int w8,
                    const void* scale, int ksplit, float* part, wm_stream_t stream) {
     GemmSkinnyParams p{};

@@ -177,6 +177,10 @@ int launch_mel_windows(const h16* const* src, const int32_t* src_frames, const i
 // resample.hip: interleaved PCM (dtype 0 f32, 1 i16, 2 i32) -> mono fp32 at L / M times the rate, table fp32 [2 half + 1][L]
 int launch_resample(const void* pcm, int dtype, int channels, long n_in, float scale, const float* table, int L, int M, int half,
                     float* out, long n_out, hipStream_t stream);
+// forced_probs.hip: out[b][p] = exp(x[b][p][clamp(next[b][p], 0, limit - 1)] - logsumexp_{v < limit} x[b][p][v]), x = logits +
+// b * stride_b + p * stride_p (elements); one workgroup per (b, p); a row of -inf gives 0
+int launch_forced_probs(const h16* logits, long stride_b, long stride_p, int batch, int n_pos, int limit, const int32_t* next,
+                        int next_ld, float* out, int out_ld, hipStream_t stream);
 int launch_layernorm(const h16* x, int ldx, int M, int N, const h16* g, const h16* b, h16* out, int ldo,
                      hipStream_t stream);
 

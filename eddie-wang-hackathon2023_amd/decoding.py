@@ -1564,7 +1564,7 @@ class WhisperDecoding:
         self.last_alignment = kept
         return out
 
-    def word_timestamps(self, audio_features, results, num_frames=None) -> List[List[timing.WordTiming]]:
+    def word_timestamps(self, audio_features, results, num_frames=None, token_probs: str = "torch") -> List[List[timing.WordTiming]]:
         """When each word of `results` (the DecodingResults of post_process for `audio_features`) was spoken: upstream
         Whisper's find_alignment on the device.  A second, teacher-forced pass over sot_sequence + <|notimestamps|> + text + EOT
         (4 tokens per call, wm_decoder_step_tap) records the cross-attention queries of the alignment heads; wm_align turns
@@ -1572,7 +1572,12 @@ class WhisperDecoding:
         reads the word boundaries off the path.  The pass reuses main_loop's cross K/V (same features: nothing is recomputed)
         and its self-attention cache buffers, so no decode may be in flight.  `num_frames`: mel frames of real audio per
         utterance (default: the whole window).  Beam search / best_of (n_group > 1) is not supported here in this version
-        (their rows' cross K/V are interleaved per candidate): use torch_word_timestamps."""
+        (their rows' cross K/V are interleaved per candidate): use torch_word_timestamps.
+        `token_probs`: where the probability of every forced token is computed from the pass's logits -- "torch" (the default:
+        an fp32 copy of each call's slab, logsumexp and gather) or "device" (wm_forced_probs, csrc/forced_probs.hip: the fp16
+        logits read once; long-form transcription uses it).  The two agree to fp32 rounding, not bit for bit."""
+        if token_probs not in ("torch", "device"):
+            raise ValueError(f"word_timestamps: token_probs = {token_probs!r}: 'torch' or 'device'")
         if self.n_group > 1:
             raise ValueError("word_timestamps: beam_size / best_of > 1 is not supported on the device path in this version "
                              "(torch_word_timestamps has no such limit)")
@@ -1619,6 +1624,10 @@ class WhisperDecoding:
                 sess.decoder_step_tap(rows[lo:hi, off:off + l], pos[off:off + l], cr, kv if off else None, cap, kv, cap, lg, off,
                                       stream, tape[lo:hi], heads_arr, slot=1000 + g)
                 # the probability the pass gives the token that follows, over the text tokens only ([:eot]); no [B, L, V] tensor
+                if token_probs == "device":
+                    native.check(lib.wm_forced_probs(lg.data_ptr(), hi - lo, l, V, l * V, V, eot, rows[lo:hi, off + 1:].data_ptr(),
+                                                     L + 1, probs[lo:hi, off:].data_ptr(), L, stream), "wm_forced_probs")
+                    continue
                 lf = lg[:, :, :eot].float()
                 nxt = rows[lo:hi, off + 1: off + l + 1].long().clamp(max=eot - 1)
                 probs[lo:hi, off:off + l] = (lf.gather(-1, nxt[..., None])[..., 0] - lf.logsumexp(dim=-1)).exp()

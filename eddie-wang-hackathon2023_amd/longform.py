@@ -22,11 +22,18 @@ the last n_text_ctx // 2 - 1 of them); a window that settles appends its segment
 forgets everything so far (reset_since = len(history)) when conditioning is off or the standing result was drawn above
 temperature 0.5; a skipped window changes nothing.  Every call of a window's ladder sees the same prompt.  With neither option
 set the decoder callbacks are called exactly as before; with either they receive the prompt(s) as one more argument.
+
+Word timestamps ("words").  Upstream's `add_word_timestamps`, restated as `add_word_timestamps` below: a
+window whose result stands and whose segments hold text is aligned once (the aligner is a callable handed in, like the decoder:
+`align_one` / `align_call`), the words are handed out to the window's segments, a few duration heuristics move word and segment
+boundaries, and the end of the window's last word, not the last timestamp pair, says where the next window begins
+(`settle_words`).  `last_speech_timestamp` is kept per file.  Without an aligner nothing of this runs and a segment has no
+"words" key.
 """
 from __future__ import annotations
 
 from collections import deque
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 CHUNK_LENGTH = 30
@@ -151,6 +158,124 @@ def settle_window(result, tb: int, seek: int, segment_size: int, fs: float, th: 
     return segments, advance
 
 
+SENTENCE_END_MARKS = ".。!！?？"
+
+
+def text_tokens(segments: Sequence[dict], eot: int) -> List[int]:
+    """The tokens below `eot` of a window's segments, in order: what the aligner aligns."""
+    return [int(t) for s in segments for t in s["tokens"] if int(t) < eot]
+
+
+def add_word_timestamps(segments: List[dict], alignment: Sequence, last_speech_timestamp: float, *, eot: int, fs: float) -> float:
+    """Upstream's add_word_timestamps for one window, in place on `segments`; returns the new last_speech_timestamp.
+
+    `segments`: the window's segments from `cut_segments` (all of one seek); `alignment`: the window's words (timing.WordTiming:
+    word, tokens, start, end, probability), times in seconds from the window's start; `eot`: tokens below it are text; `fs`:
+    seconds per frame.  The alignment is read, never written: the entries the rules move are copies.
+
+      1. a segment's text tokens are its tokens below `eot` (a cleared segment has none);
+      2. durations = the nonzero end - start of the alignment; median = min(0.7, median(durations)), 0.0 without durations;
+         max_duration = 2 * median;
+      3. (only with durations) for i >= 1 with end_i - start_i > max_duration: word_i a sentence mark (one of .。!！?？):
+         end_i = start_i + max_duration; else word_{i-1} a sentence mark: start_i = end_i - max_duration;
+      4. one walk over the alignment: a segment takes words until the tokens taken reach its text-token count; a taken word
+         becomes {word, start, end, probability}, times + seek * fs and rounded to 2 decimals;
+      5. per segment with words, in this order: the after-pause clamp, the segment-start rule, the segment-end rule (the code
+         below is their statement), then last_speech_timestamp = segment.end;
+      6. every segment gets segment["words"], possibly [].
+
+    Order of step 3 and the punctuation merge.  Upstream truncates first and merges afterwards; here the alignment arrives
+    MERGED (timing.words_from_path has applied merge_punctuations and dropped the absorbed entries), and step 3 runs on it as it
+    stands: merge, then truncate.  A closing mark that followed a word is part of that word by then ("end." is not a mark), so
+    step 3 fires only for a mark that stands alone -- the first entry, or one behind a word that ends in a blank -- and for the
+    word after such a mark.  Words are compared as they are, without stripping, as upstream."""
+    words_in = [replace(w) for w in alignment]
+    durations = sorted(w.end - w.start for w in words_in if w.end - w.start != 0)
+    if durations:
+        mid = len(durations) // 2
+        median = durations[mid] if len(durations) % 2 else 0.5 * (durations[mid - 1] + durations[mid])
+        median = min(0.7, float(median))
+    else:
+        median = 0.0
+    max_duration = 2 * median
+
+    def is_mark(word: str) -> bool:
+        return len(word) == 1 and word in SENTENCE_END_MARKS
+
+    if durations:
+        for i in range(1, len(words_in)):
+            w = words_in[i]
+            if w.end - w.start > max_duration:
+                if is_mark(w.word):
+                    w.end = w.start + max_duration
+                elif is_mark(words_in[i - 1].word):
+                    w.start = w.end - max_duration
+
+    time_offset = (segments[0]["seek"] * fs) if segments else 0.0
+    index = 0
+    for segment in segments:
+        n_text = sum(1 for t in segment["tokens"] if int(t) < eot)
+        taken = 0
+        words: List[dict] = []
+        while index < len(words_in) and taken < n_text:
+            w = words_in[index]
+            if w.word:
+                words.append(dict(word=w.word, start=round(time_offset + w.start, 2), end=round(time_offset + w.end, 2),
+                                  probability=w.probability))
+            taken += len(w.tokens)
+            index += 1
+        if words:
+            first = words[0]
+            # after a pause: the first word (or the first two) of the segment cannot be longer than two medians
+            if first["end"] - last_speech_timestamp > 4 * median and (
+                    first["end"] - first["start"] > max_duration
+                    or (len(words) > 1 and words[1]["end"] - first["start"] > 2 * max_duration)):
+                if len(words) > 1 and words[1]["end"] - words[1]["start"] > max_duration:
+                    boundary = max(words[1]["end"] / 2, words[1]["end"] - max_duration)
+                    first["end"] = words[1]["start"] = boundary
+                first["start"] = max(0, first["end"] - max_duration)
+            # segment start: the timestamp token wins when it lies inside the first word and well behind its start
+            if segment["start"] < first["end"] and segment["start"] - 0.5 > first["start"]:
+                first["start"] = max(0, min(first["end"] - median, segment["start"]))
+            else:
+                segment["start"] = first["start"]
+            # segment end, likewise
+            last = words[-1]
+            if segment["end"] > last["start"] and segment["end"] + 0.5 < last["end"]:
+                last["end"] = max(last["start"] + median, segment["end"])
+            else:
+                segment["end"] = last["end"]
+            last_speech_timestamp = segment["end"]
+        segment["words"] = words
+    return last_speech_timestamp
+
+
+def settle_words(segments: List[dict], alignment: Sequence, tokens: Sequence[int], tb: int, seek: int, segment_size: int,
+                 fs: float, eot: int, advance: int, last_speech_timestamp: float) -> Tuple[int, float]:
+    """A window with segments, once aligned: `add_word_timestamps`, then upstream's seek rule for words -- (advance,
+    last_speech_timestamp).  last_word_end is the end of the last word of the last segment that has words; unless the window
+    ended on a single timestamp, a last_word_end behind the window's start moves the next window to round(last_word_end / fs),
+    through the guard of `cut_segments` (<= 0 or > segment_size: the whole window); a last_word_end, wherever it lies, becomes
+    the file's last_speech_timestamp.  Without segments nothing changes."""
+    if not segments:
+        return advance, last_speech_timestamp
+    last_speech_timestamp = add_word_timestamps(segments, alignment, last_speech_timestamp, eot=eot, fs=fs)
+    last_word_end = next((s["words"][-1]["end"] for s in reversed(segments) if s["words"]), None)
+    if last_word_end is None:
+        return advance, last_speech_timestamp
+    single_end = _timestamp_pairs([int(t) for t in tokens], tb)[0]
+    if not single_end and last_word_end > seek * fs:
+        advance = round(last_word_end / fs) - seek
+        if advance <= 0 or advance > segment_size:     # the guard (module docstring)
+            advance = segment_size
+    return advance, last_word_end
+
+
+def _check_aligner(aligner, eot) -> None:
+    if aligner is not None and eot is None:
+        raise ValueError("word timestamps: an aligner needs `eot` (tokens below it are the text that is aligned)")
+
+
 class PromptHistory:
     """The tokens a file's later windows are conditioned on (module docstring)."""
 
@@ -186,10 +311,16 @@ def transcribe_reference(decode_one: Callable[[int, float], object], content_fra
                          temperatures: Sequence[float] = TEMPERATURES, compression_ratio_threshold: Optional[float] = 2.4,
                          logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
                          decode_text: Optional[Callable[[List[int]], str]] = None, condition_on_previous_text: bool = False,
-                         initial_prompt: Sequence[int] = ()) -> List[dict]:
+                         initial_prompt: Sequence[int] = (), align_one: Optional[Callable[[int, int, List[dict]], Sequence]] = None,
+                         eot: Optional[int] = None) -> List[dict]:
     """The literal loop for one file of `content_frames` frames: `decode_one(seek, temperature)` decodes the window at `seek`.
-    With `condition_on_previous_text` or an `initial_prompt` (token ids): `decode_one(seek, temperature, prompt)`."""
+    With `condition_on_previous_text` or an `initial_prompt` (token ids): `decode_one(seek, temperature, prompt)`.
+    With `align_one` (and `eot`): every segment gets "words".  `align_one(seek, segment_size, segments)` returns the alignment
+    of a window (`add_word_timestamps`); it is asked once per window whose segments hold text, a window with segments but no
+    text has the empty alignment, and a window that is skipped or has no segments is left alone (`settle_words`)."""
     temperatures = _check_ladder(temperatures)
+    _check_aligner(align_one, eot)
+    last_speech = 0.0
     prompted = bool(condition_on_previous_text) or len(initial_prompt) > 0
     history = PromptHistory(initial_prompt, condition_on_previous_text)
     th = _thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold)
@@ -206,6 +337,10 @@ def transcribe_reference(decode_one: Callable[[int, float], object], content_fra
                 break
         cut, advance = settle_window(result, timestamp_begin, seek, segment_size, fs, th, decode_text)
         history.settle(result, cut, skip_window(result, th.logprob_threshold, th.no_speech_threshold))
+        if align_one is not None and cut:
+            alignment = align_one(seek, segment_size, cut) if text_tokens(cut, eot) else []
+            advance, last_speech = settle_words(cut, alignment, result.tokens, timestamp_begin, seek, segment_size, fs, eot,
+                                                advance, last_speech)
         segments += cut
         seek += advance
     return segments
@@ -220,7 +355,10 @@ def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], f
                        temperatures: Sequence[float] = TEMPERATURES, compression_ratio_threshold: Optional[float] = 2.4,
                        logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
                        decode_text: Optional[Callable[[List[int]], str]] = None, condition_on_previous_text: bool = False,
-                       initial_prompt: Sequence[int] = ()) -> List[List[dict]]:
+                       initial_prompt: Sequence[int] = (),
+                       align_call: Optional[Callable[[List[Optional[Tuple[int, int]]], List[Optional[Tuple[int, List[int]]]]],
+                                                     Sequence[Sequence]]] = None,
+                       eot: Optional[int] = None) -> List[List[dict]]:
     """The scheduler: up to `n_rows` files are active, one row each; every round decodes the current window of each.
 
     `decode_call(rows, temperature, live)`: rows[i] = (file, seek) of row i or None for an empty row, always n_rows of them;
@@ -232,8 +370,15 @@ def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], f
 
     With `condition_on_previous_text` or an `initial_prompt` (token ids, the same for every file):
     `decode_call(rows, temperature, live, prompts)`, prompts[i] the prompt of row i's window ([] for an empty row); the fallback
-    calls of a round carry the round's prompts."""
+    calls of a round carry the round's prompts.
+
+    With `align_call` (and `eot`): every segment gets "words", as in `transcribe_reference`.  `align_call(rows, jobs)`: rows as
+    above, jobs[i] = None or (segment_size, the text tokens of the segments of row i's standing result), always n_rows of them;
+    returns n_rows alignments (anything for a row without a job).  It is asked at most once per round, after the ladder has
+    settled every row, and not at all in a round in which no row has text."""
     temperatures = _check_ladder(temperatures)
+    _check_aligner(align_call, eot)
+    last_speech: Dict[int, float] = {}
     if n_rows < 1:
         raise ValueError(f"n_rows = {n_rows}: need at least one row")
     th = _thresholds(compression_ratio_threshold, logprob_threshold, no_speech_threshold)
@@ -251,6 +396,7 @@ def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], f
                 rows[i] = waiting.popleft()
                 seek[rows[i]] = 0
                 history[rows[i]] = PromptHistory(initial_prompt, condition_on_previous_text)
+                last_speech[rows[i]] = 0.0
         if all(f is None for f in rows):
             break
         asked = [None if f is None else (f, seek[f]) for f in rows]
@@ -268,12 +414,31 @@ def transcribe_batched(decode_call: Callable[[List[Optional[Tuple[int, int]]], f
                 if need[i]:
                     final[i] = again[i]
                     need[i] = needs_fallback(again[i], *_astuple(th))
+        settled: List[Optional[Tuple[int, List[dict], int]]] = [None] * n_rows       # (segment_size, segments, advance)
         for i, f in enumerate(rows):
             if f is None:
                 continue
             segment_size = min(window, content[f] - seek[f])
             cut, advance = settle_window(final[i], timestamp_begin, seek[f], segment_size, fs, th, decode_text)
             history[f].settle(final[i], cut, skip_window(final[i], th.logprob_threshold, th.no_speech_threshold))
+            settled[i] = (segment_size, cut, advance)
+        if align_call is not None:
+            jobs: List[Optional[Tuple[int, List[int]]]] = [None] * n_rows
+            for i, s in enumerate(settled):
+                if s is not None and text_tokens(s[1], eot):
+                    jobs[i] = (s[0], text_tokens(s[1], eot))
+            alignments = list(align_call(list(asked), list(jobs))) if any(j is not None for j in jobs) else [None] * n_rows
+            for i, f in enumerate(rows):
+                if f is None or not settled[i][1]:
+                    continue
+                segment_size, cut, advance = settled[i]
+                advance, last_speech[f] = settle_words(cut, alignments[i] if jobs[i] is not None else [], final[i].tokens,
+                                                       timestamp_begin, seek[f], segment_size, fs, eot, advance, last_speech[f])
+                settled[i] = (segment_size, cut, advance)
+        for i, f in enumerate(rows):
+            if f is None:
+                continue
+            _, cut, advance = settled[i]
             segments[f] += cut
             seek[f] += advance
             if seek[f] >= content[f]:

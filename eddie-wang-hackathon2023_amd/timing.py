@@ -10,7 +10,8 @@ Everything here runs on the CPU and is what the device path (csrc/align.hip: wm_
   `words_from_path`   step 9
 
 Two deliberate differences from upstream: a frame whose weights have no spread over the tokens (std == 0) gets Z = 0 where
-upstream divides by zero, and nothing of upstream's long-form heuristics (`add_word_timestamps`' duration clamps) is applied.
+upstream divides by zero, and nothing of upstream's long-form heuristics (`add_word_timestamps`' duration clamps) is applied
+here: they are longform.add_word_timestamps, which long-form transcription applies to what `words_from_path` returns.
 """
 from __future__ import annotations
 

@@ -20,18 +20,28 @@ longform.py states the contract (the rules and the schedule, on the host, tested
     (WhisperDecoding.set_prompts: right-aligned rows).  They need an instance built with `row_prompts=True`, whose start
     length is fixed at construction.
 
+  * `word_timestamps`: after a round's ladder has settled every row, ONE WhisperDecoding.word_timestamps call over the round's
+    rows (token_probs="device": wm_forced_probs) aligns the text of every row's standing segments on the round's own features --
+    the cross K/V stay in place, the encoder still runs once per round -- and longform.settle_words hands the words to the
+    segments and lets the last word's end say where the file's next window begins.  Rows without text have no tokens and are
+    skipped by wm_align.  The tap pass is left-aligned and starts from sot_sequence, so it runs on a `row_prompts` instance too.
+
 Refused (ValueError): an instance built with `prompt` / `prefix` (use `initial_prompt`), conditioning or an initial prompt on
-an instance without `row_prompts`, and beam_size / best_of together with a ladder of more than one temperature.  Out of scope: word
-timestamps per segment, clip_timestamps, the hallucination-silence heuristics.  Files at any rate from 4 kHz to 192 kHz and with
+an instance without `row_prompts`, beam_size / best_of together with a ladder of more than one temperature, and word timestamps
+with beam_size / best_of; word timestamps on an engine with int8 cross K/V raise WhisperDecoding.word_timestamps' own error.  Out of
+scope: clip_timestamps, the hallucination-silence heuristics (hallucination_silence_threshold).  Files at any rate from 4 kHz to 192 kHz and with
 several channels are downmixed and resampled to 16 kHz on the device (whisper_utils.load_audio_device, wm_resample).
 
 CLI: python transcribe.py --engine_dir eng --input_file a.flac [b.flac ...] --vocab multilingual.tiktoken [--temperature T ...]
-[--no_fallback] [--condition_on_previous_text] [--initial_prompt TEXT] prints one "[mm:ss.mmm --> mm:ss.mmm] text" line per non-empty segment.
+[--no_fallback] [--condition_on_previous_text] [--initial_prompt TEXT] [--word_timestamps] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
+line per non-empty segment, and with --word_timestamps one "start-end word (probability)" line per word under it.
 """
 from __future__ import annotations
 
 import argparse
+import copy
 import logging
+import types
 from pathlib import Path
 from typing import List, Optional, Sequence
 
@@ -46,9 +56,15 @@ from tokenizer import Tokenizer
 
 
 def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], condition_on_previous_text: bool = False,
-                    initial_prompt=None) -> None:
+                    initial_prompt=None, word_timestamps: bool = False) -> None:
     """The combinations this version refuses (module docstring)."""
     opt = decoding.options
+    if word_timestamps:
+        if decoding.beam or decoding.n_group != 1:
+            raise ValueError("transcribe: word_timestamps with beam_size / best_of is not supported in this version (the device "
+                             "alignment reads one row of cross K/V per file)")
+        if getattr(decoding, 'use_int8_cross_kv', False):
+            raise native.WmError("word timestamps need fp16 cross-attention K/V; this engine stores int8 codes (WM_FLAG_INT8_CROSS_KV)")
     if opt.prompt or opt.prefix:
         raise ValueError("transcribe: an instance built with options.prompt / options.prefix is not supported: hand the prompt to "
                          "transcribe(initial_prompt=...) with an instance built with row_prompts=True")
@@ -83,10 +99,22 @@ def mel_windows(mels: Sequence[Optional[torch.Tensor]], seeks: Sequence[int], n_
     return out
 
 
-def default_rows(decoding: WhisperDecoding, n_files: int, device) -> int:
-    """min(files, what fits): the decoder state of a row (state_bytes_per_utterance) against four fifths of the free memory."""
+def word_pass_bytes_per_row(decoding: WhisperDecoding) -> int:
+    """What a row of the word-timestamp pass holds beside the decoder state: the tape of the alignment heads' queries
+    (heads x L_max x 64 fp16 = 128 B each, L_max the longest forced sequence: sot_sequence + <|notimestamps|> + sample_len + EOT,
+    at most n_text_ctx) and the fp16 logits of a 4-token call."""
+    cfg = decoding.decoder_config
+    l_max = min(cfg['num_text_ctx'], len(decoding.tokenizer.sot_sequence) + 2 + int(decoding.sample_len))
+    return len(decoding.alignment_heads()) * l_max * 128 + 4 * cfg['vocab_size'] * 2
+
+
+def default_rows(decoding: WhisperDecoding, n_files: int, device, word_timestamps: bool = False) -> int:
+    """min(files, what fits): the decoder state of a row (state_bytes_per_utterance; with word timestamps plus
+    word_pass_bytes_per_row) against four fifths of the free memory."""
     free, _ = torch.cuda.mem_get_info(device)
     per_row = decoding.state_bytes_per_utterance() * decoding.n_group
+    if word_timestamps:
+        per_row += word_pass_bytes_per_row(decoding)
     return max(1, min(n_files, int(0.8 * free // per_row)))
 
 
@@ -94,7 +122,7 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
                    content_frames: Sequence[int], *, temperatures: Sequence[float] = longform.TEMPERATURES,
                    compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
                    no_speech_threshold: Optional[float] = 0.6, n_rows: Optional[int] = None, trace: Optional[list] = None,
-                   condition_on_previous_text: bool = False, initial_prompt=None) -> List[dict]:
+                   condition_on_previous_text: bool = False, initial_prompt=None, word_timestamps: bool = False) -> List[dict]:
     """Transcribe files given as log-mels: mels[f] fp16 [n_mels, content_frames[f] + W] on the GPU (W = 2 * n_audio_ctx; the last
     W frames are the log-mel of 30 s of padding: whisper_utils.long_log_mel_device).  One dict per file: language, text, segments;
     a segment: seek, start, end (seconds), text, tokens, temperature, avg_logprob, compression_ratio, no_speech_prob.
@@ -102,9 +130,12 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
     call (rows, live, temperature, windows, results, prompts, ...: tests, diagnostics).
     `condition_on_previous_text`: every window of a file is decoded with the file's text so far as its prompt (upstream's rules,
     longform.py; off by default, unlike upstream).  `initial_prompt`: a string or token ids, the prompt of every file's first
-    window (and, with conditioning, the head of its history)."""
+    window (and, with conditioning, the head of its history).
+    `word_timestamps`: every segment also carries `words`, a list of {word, start, end (seconds), probability} (possibly empty);
+    segment starts and ends and the seeks follow the words (longform.add_word_timestamps / settle_words).  `trace` then also
+    receives one dict per alignment call: kind = "align", round, rows, jobs, languages, alignments (as the device returned them)."""
     temperatures = tuple(float(t) for t in (temperatures if isinstance(temperatures, (tuple, list)) else [temperatures]))
-    check_supported(decoding, temperatures, condition_on_previous_text, initial_prompt)
+    check_supported(decoding, temperatures, condition_on_previous_text, initial_prompt, word_timestamps)
     if isinstance(initial_prompt, str):
         initial_prompt = decoding.tokenizer.encode(" " + initial_prompt.strip())
     initial_prompt = [int(t) for t in (initial_prompt if initial_prompt is not None else ())]
@@ -124,7 +155,7 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
     dev = mels[0].device
     mels = [m.to(torch.float16).contiguous() for m in mels]
     if n_rows is None:
-        n_rows = default_rows(decoding, max(1, sum(1 for c in content_frames if c > 0)), dev)
+        n_rows = default_rows(decoding, max(1, sum(1 for c in content_frames if c > 0)), dev, word_timestamps)
     n_group = decoding.n_group
 
     # the language of every file: named by the options, or detected on the file's first window
@@ -182,10 +213,22 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
                               n_states=len(decoding._state), n_graphs=len(st['graphs'])))
         return results
 
+    def align_call(rows, jobs):
+        assert len(jobs) == n_rows and state['rows'] == list(rows), "an alignment belongs to the round that was decoded last"
+        sampled = [types.SimpleNamespace(tokens=[] if j is None else list(j[1]), language=lang)
+                   for j, lang in zip(jobs, state['languages'])]
+        frames = [0 if j is None else int(j[0]) for j in jobs]
+        alignments = decoding.word_timestamps(state['features'], sampled, frames, token_probs="device")
+        if trace is not None:
+            trace.append(dict(kind="align", round=state['round'], rows=list(rows), jobs=copy.deepcopy(list(jobs)),
+                              languages=list(state['languages']), alignments=copy.deepcopy(alignments)))
+        return alignments
+
+    words = dict(align_call=align_call, eot=tk.eot) if word_timestamps else {}
     segments = longform.transcribe_batched(
         decode_call, [int(c) for c in content_frames], n_rows, window=W, timestamp_begin=tk.timestamp_begin,
         temperatures=temperatures, compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
-        no_speech_threshold=no_speech_threshold, decode_text=tk.decode,
+        no_speech_threshold=no_speech_threshold, decode_text=tk.decode, **words,
         **(dict(condition_on_previous_text=bool(condition_on_previous_text), initial_prompt=initial_prompt) if prompted else {}))
     out = []
     for f in range(n_files):
@@ -229,6 +272,8 @@ def parse_arguments(argv=None):
     parser.add_argument('--condition_on_previous_text', default=False, action='store_true',
                         help="decode every window with the file's text so far as its prompt (upstream's default; off here)")
     parser.add_argument('--initial_prompt', type=str, default=None, help="text in front of every file's first window: names, spelling, style")
+    parser.add_argument('--word_timestamps', default=False, action='store_true',
+                        help='print "start-end word (probability)" lines under every segment (cross-attention alignment + DTW on the device; greedy decoding only)')
     return parser.parse_args(argv)
 
 
@@ -241,13 +286,16 @@ def main(args) -> List[dict]:
     decoding = WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language), row_prompts=prompted)
     temperatures = tuple(args.temperature[:1] if args.no_fallback else args.temperature)
     results = transcribe(encoding, decoding, args.input_file, temperatures=temperatures, n_rows=args.rows,
-                         condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt)
+                         condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt,
+                         word_timestamps=args.word_timestamps)
     for path, result in zip(args.input_file, results):
         if len(results) > 1:
             print(f"{path} ({result['language']})")
         for s in result['segments']:
             if s['text'].strip():
                 print(f"[{format_timestamp(s['start'])} --> {format_timestamp(s['end'])}] {s['text'].strip()}")
+                for w in s.get('words', ()):
+                    print(f"{w['start']:.2f}\u2013{w['end']:.2f} {w['word'].strip()} ({w['probability']:.2f})")
     return results
 
 

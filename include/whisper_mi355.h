@@ -62,7 +62,8 @@ typedef struct wm_dims {
  *      wm_decode_chain_error has been called; wm_decode_chain_status, wm_debug_occupy
  *   8  (round 6) wm_decoder_io gains `not_alone` (appended): the caller says when other decoder steps may run beside this one
  *      (still 8, like wm_mel_windows / wm_resample) wm_decoder_io gains `row_start` (appended; NULL = as before); wm_attn_decode_self_rows
- *      (still 8: test-only entries, no existing struct or signature changed) wm_attn_self_ex, wm_attn_cross_ex */
+ *      (still 8: test-only entries, no existing struct or signature changed) wm_attn_self_ex, wm_attn_cross_ex
+ *      (still 8: an entry only) wm_forced_probs */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -460,6 +461,14 @@ int wm_mel_transpose_pad(const void* mel, int B, int n_mels, int T, void* out, w
  * capturable.  Added under ABI 8 (an entry only; no struct changes). */
 int wm_mel_windows(const void* const* src, const int32_t* src_frames, const int32_t* seek, int batch, int n_mels, int n_window,
                    void* out, wm_stream_t stream);
+/* The probability a teacher-forced pass gives the token that follows, over the first `limit` entries of the vocabulary:
+ *   out[b * out_ld + p] = exp(x[min(next[b * next_ld + p], limit - 1)] - logsumexp_{v < limit} x[v]),   x = logits + b * stride_b + p * stride_p
+ * for b < batch, p < n_pos.  logits: fp16, strides in elements (stride_p >= n_vocab; rows may start at any 2-byte address); next:
+ * DEVICE int32 (a negative entry reads x[0]); out: DEVICE fp32; 1 <= limit <= n_vocab.  The logits are read once, as fp16; sums are
+ * fp32 and merged in a fixed order (the same bits on every run); a row whose logits below `limit` are all -inf gives 0.
+ * Added under ABI 8 (an entry only; no struct changes). */
+int wm_forced_probs(const void* logits, int batch, int n_pos, int n_vocab, int64_t stride_b, int64_t stride_p, int limit,
+                    const int32_t* next, int next_ld, float* out, int out_ld, wm_stream_t stream);
 /* zeroes rows 0 and Tpad - 1 of every utterance of buf fp16 [B][Tpad][C]. */
 int wm_zero_pad_rows(void* buf, int B, int Tpad, int C, wm_stream_t stream);
 /* ids[b] = arg-max of row b of fp16 logits (first index wins ties).  The decode loop itself uses

@@ -2,7 +2,9 @@
   (1) wm_mel_windows at the product shape, 576 x 80 x 3000 with odd seeks into files of odd length, beside a hipMemcpyAsync
       (torch's device-to-device copy_) of the same bytes, both in GB/s of bytes read + written;
   (2) a job of N synthetic files through transcribe.transcribe_mel with the fallback off, beside the same windows, round by
-      round, through get_audio_features -> main_loop -> post_process at the same row count.
+      round, through get_audio_features -> main_loop -> post_process at the same row count;
+  (3) the same job with word_timestamps=True (one alignment call per round; the last word's end moves the windows, so the job
+      has windows and rounds of its own: both are reported, and the time per round beside (2)'s).
       python scripts/bench_longform.py [files=16] [windows_per_file=3] [tokens=32] [engine_dir]
 Without an engine directory: the large-v2 engines `bench.py --engine-cache /tmp/wm_bench_engines` keeps when they exist, else
 a `tiny`-shaped engine with seeded random weights built into a temporary directory."""
@@ -106,4 +108,17 @@ report["job"] = dict(engine=shape or str(eng), files=N, rows=N, windows=n_window
                      transcribe_mel_ms=ms_job, plain_main_loop_ms=ms_plain)
 print(f"{shape or eng}: {N} files, {n_windows} windows in {len(rounds)} rounds of {N} rows, sample_len {TOKENS}: transcribe_mel {ms_job:.1f} ms, "
       f"the same windows through get_audio_features + main_loop + post_process {ms_plain:.1f} ms ({ms_job / ms_plain:.2f} x)")
+
+# ---- (3) the same job with word timestamps
+trace_w = []
+T.transcribe_mel(enc, dec, mels, content, trace=trace_w, word_timestamps=True, **kw)
+rounds_w = [e for e in trace_w if e.get("kind") != "align" and e["new_round"]]
+aligns_w = [e for e in trace_w if e.get("kind") == "align"]
+windows_w = sum(sum(e["live"]) for e in rounds_w)
+ms_words = wall_ms(lambda: T.transcribe_mel(enc, dec, mels, content, word_timestamps=True, **kw), reps=2)
+report["job_words"] = dict(engine=shape or str(eng), files=N, rows=N, windows=windows_w, rounds=len(rounds_w), alignment_calls=len(aligns_w),
+                           tokens=TOKENS, transcribe_mel_ms=ms_words, ms_per_round=ms_words / len(rounds_w),
+                           ms_per_round_without_words=ms_job / len(rounds))
+print(f"{shape or eng}: the same files with word_timestamps=True: {windows_w} windows in {len(rounds_w)} rounds, {len(aligns_w)} alignment calls: "
+      f"transcribe_mel {ms_words:.1f} ms = {ms_words / len(rounds_w):.2f} ms per round (without words: {ms_job / len(rounds):.2f} ms per round)")
 print(json.dumps(report))
