@@ -181,6 +181,11 @@ int launch_resample(const void* pcm, int dtype, int channels, long n_in, float s
 // b * stride_b + p * stride_p (elements); one workgroup per (b, p); a row of -inf gives 0
 int launch_forced_probs(const h16* logits, long stride_b, long stride_p, int batch, int n_pos, int limit, const int32_t* next,
                         int next_ld, float* out, int out_ld, hipStream_t stream);
+// sections.hip: the cuts of a ragged batch of whole-file log-mels (sections.py: loudness, smoothing, quietest frame per range)
+size_t section_cuts_workspace_bytes(int batch, long long total_frames);
+int launch_section_cuts(const void* const* src, const int32_t* src_ld, const int32_t* content, int batch, int n_mels, int lo,
+                        int hi, int h, int32_t* cuts, int cuts_ld, int32_t* n_cuts, void* workspace, long long total_frames,
+                        hipStream_t stream);
 int launch_layernorm(const h16* x, int ldx, int M, int N, const h16* g, const h16* b, h16* out, int ldo,
                      hipStream_t stream);
 

@@ -85,6 +85,7 @@ EXPORTS = (
     "wm_mel_windows", "wm_resample", "wm_attn_decode_self_rows",
     "wm_attn_self_ex", "wm_attn_cross_ex",
     "wm_forced_probs",
+    "wm_section_cuts_workspace_bytes", "wm_section_cuts",
 )
 
 
@@ -383,6 +384,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_mel_windows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.wm_resample.argtypes = [vp, i32, i32, C.c_int64, C.c_float, vp, i32, i32, i32, vp, C.c_int64, vp]
     lib.wm_forced_probs.argtypes = [vp, i32, i32, i32, C.c_int64, C.c_int64, i32, vp, i32, vp, i32, vp]
+    lib.wm_section_cuts_workspace_bytes.argtypes = [i32, C.c_int64]
+    lib.wm_section_cuts_workspace_bytes.restype = sz
+    lib.wm_section_cuts.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, C.c_int64, vp]
     lib.wm_decoder_step_tap.argtypes = [vp, C.POINTER(WmDecoderIO), C.POINTER(WmTapIO), vp]
     lib.wm_align_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.wm_align_workspace_bytes.restype = sz

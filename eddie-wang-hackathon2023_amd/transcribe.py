@@ -26,6 +26,13 @@ longform.py states the contract (the rules and the schedule, on the host, tested
     segments and lets the last word's end say where the file's next window begins.  Rows without text have no tokens and are
     skipped by wm_align.  The tap pass is left-aligned and starts from sot_sequence, so it runs on a `row_prompts` instance too.
 
+  * `sections` (sections.SectionOptions): a long file is cut where it is quietest (wm_section_cuts,
+    csrc/sections.hip: one launch and one copy back for all files) and its sections take the rows that files take otherwise, so
+    ONE long recording fills the batch.  A file has one language -- named, or detected on the first window of its FIRST section
+    and used by all of them; `initial_prompt` heads every section; word timestamps are aligned per section; the sections'
+    segments are shifted and joined by sections.merge_sections.  Unlike upstream, nothing crosses a cut: sections run side by
+    side, so `condition_on_previous_text` keeps its history per section.  Without the option nothing of this runs.
+
 Refused (ValueError): an instance built with `prompt` / `prefix` (use `initial_prompt`), conditioning or an initial prompt on
 an instance without `row_prompts`, beam_size / best_of together with a ladder of more than one temperature, and word timestamps
 with beam_size / best_of; word timestamps on an engine with int8 cross K/V raise WhisperDecoding.word_timestamps' own error.  Out of
@@ -33,7 +40,8 @@ scope: clip_timestamps, the hallucination-silence heuristics (hallucination_sile
 several channels are downmixed and resampled to 16 kHz on the device (whisper_utils.load_audio_device, wm_resample).
 
 CLI: python transcribe.py --engine_dir eng --input_file a.flac [b.flac ...] --vocab multilingual.tiktoken [--temperature T ...]
-[--no_fallback] [--condition_on_previous_text] [--initial_prompt TEXT] [--word_timestamps] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
+[--no_fallback] [--condition_on_previous_text] [--initial_prompt TEXT] [--word_timestamps] [--sections [--section_seconds S]
+[--min_section_seconds S]] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
 line per non-empty segment, and with --word_timestamps one "start-end word (probability)" line per word under it.
 """
 from __future__ import annotations
@@ -50,8 +58,10 @@ import torch
 
 import longform
 import native
+import sections as sections_mod
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
+from sections import SectionOptions
 from tokenizer import Tokenizer
 
 
@@ -118,11 +128,64 @@ def default_rows(decoding: WhisperDecoding, n_files: int, device, word_timestamp
     return max(1, min(n_files, int(0.8 * free // per_row)))
 
 
+def section_cuts(mels: Sequence[torch.Tensor], content_frames: Sequence[int], options: SectionOptions,
+                 window: int = 3000) -> List[List[int]]:
+    """The cut frames of every file, ascending (sections.section_cuts_ref on the device: ONE wm_section_cuts launch for all files on
+    the current stream and one copy of the cuts and their counts back).  mels[f]: contiguous fp16 [n_mels, >= content_frames[f]]
+    on the GPU; `window`: the model's 2 * n_audio_ctx, which fixes the seconds per frame."""
+    n = len(mels)
+    if n == 0:
+        return []
+    if len(content_frames) != n:
+        raise ValueError(f"section_cuts: {len(content_frames)} content_frames for {n} mels")
+    n_mels = int(mels[0].shape[0])
+    lo, hi, h = options.frames(window, n_mels)
+    for m, c in zip(mels, content_frames):
+        assert m.is_cuda and m.dtype == torch.float16 and m.dim() == 2 and m.shape[0] == n_mels and m.is_contiguous(), \
+            "a mel must be a contiguous fp16 [n_mels, frames] tensor on the GPU"
+        if not 0 <= c <= m.shape[1]:
+            raise ValueError(f"section_cuts: {c} frames of content in a mel of {m.shape[1]}")
+    dev = mels[0].device
+    total = int(sum(content_frames))
+    cuts_ld = max(1, max(int(c) for c in content_frames) // lo)
+    table = torch.tensor([[m.data_ptr() for m in mels], [m.shape[1] for m in mels], [int(c) for c in content_frames]],
+                         dtype=torch.int64).to(dev, non_blocking=False)
+    ld, content = table[1].to(torch.int32), table[2].to(torch.int32)
+    lib = native.load_library()
+    ws_bytes = int(lib.wm_section_cuts_workspace_bytes(n, total))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(n * (1 + cuts_ld), dtype=torch.int32, device=dev)             # n_cuts [n], then cuts [n][cuts_ld]
+    native.check(lib.wm_section_cuts(table[0].data_ptr(), ld.data_ptr(), content.data_ptr(), n, n_mels, lo, hi, h,
+                                     out[n:].data_ptr(), cuts_ld, out.data_ptr(), ws.data_ptr(), ws_bytes, total,
+                                     torch.cuda.current_stream(dev).cuda_stream), "wm_section_cuts")
+    host = out.cpu().tolist()
+    found = host[:n]
+    if any(k < 0 or k > cuts_ld for k in found):
+        raise ValueError(f"section_cuts: wm_section_cuts found {found} cuts, room for {cuts_ld} per file")
+    return [host[n + f * cuts_ld: n + f * cuts_ld + found[f]] for f in range(n)]
+
+
+def section_mels(mels: Sequence[torch.Tensor], content_frames: Sequence[int], cuts: Sequence[Sequence[int]], window: int):
+    """The sections of every file as files of their own: (section mels, their content frames, owner, starts) in file order and
+    section order; owner[i] is the file of section i and starts[i] its first frame there.  A section's mel is
+    sections.section_mel_ref's bit for bit: its frames, then `window` copies of the file's last column."""
+    out, content, owner, starts = [], [], [], []
+    for f, (m, c) in enumerate(zip(mels, content_frames)):
+        pad = m[:, -1:].expand(-1, window) if c > 0 else None
+        for a, b in sections_mod.section_bounds(int(c), cuts[f]):
+            out.append(torch.cat([m[:, a:b], pad], dim=1).contiguous())
+            content.append(b - a)
+            owner.append(f)
+            starts.append(a)
+    return out, content, owner, starts
+
+
 def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: Sequence[torch.Tensor],
                    content_frames: Sequence[int], *, temperatures: Sequence[float] = longform.TEMPERATURES,
                    compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
                    no_speech_threshold: Optional[float] = 0.6, n_rows: Optional[int] = None, trace: Optional[list] = None,
-                   condition_on_previous_text: bool = False, initial_prompt=None, word_timestamps: bool = False) -> List[dict]:
+                   condition_on_previous_text: bool = False, initial_prompt=None, word_timestamps: bool = False,
+                   sections: Optional[SectionOptions] = None) -> List[dict]:
     """Transcribe files given as log-mels: mels[f] fp16 [n_mels, content_frames[f] + W] on the GPU (W = 2 * n_audio_ctx; the last
     W frames are the log-mel of 30 s of padding: whisper_utils.long_log_mel_device).  One dict per file: language, text, segments;
     a segment: seek, start, end (seconds), text, tokens, temperature, avg_logprob, compression_ratio, no_speech_prob.
@@ -133,7 +196,65 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
     window (and, with conditioning, the head of its history).
     `word_timestamps`: every segment also carries `words`, a list of {word, start, end (seconds), probability} (possibly empty);
     segment starts and ends and the seeks follow the words (longform.add_word_timestamps / settle_words).  `trace` then also
-    receives one dict per alignment call: kind = "align", round, rows, jobs, languages, alignments (as the device returned them)."""
+    receives one dict per alignment call: kind = "align", round, rows, jobs, languages, alignments (as the device returned them).
+    `sections`: cut every file where it is quietest and decode the sections side by side (module docstring; sections.py).  The
+    rows' "files" are then the sections, in file order and section order -- `n_rows` defaults to min(sections, what fits), and
+    `trace` speaks of sections; a file's result also carries "sections": [(start, end), ...] in seconds.  Unlike upstream,
+    `condition_on_previous_text` keeps its history per section: the sections run side by side, so no text crosses a cut."""
+    kw = dict(temperatures=temperatures, compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
+              no_speech_threshold=no_speech_threshold, n_rows=n_rows, trace=trace, condition_on_previous_text=condition_on_previous_text,
+              initial_prompt=initial_prompt, word_timestamps=word_timestamps)
+    if sections is not None:
+        return _transcribe_sections(encoding, decoding, mels, content_frames, sections, **kw)
+    return _transcribe_files(encoding, decoding, mels, content_frames, None, **kw)
+
+
+def _transcribe_sections(encoding, decoding, mels, content_frames, options: SectionOptions, **kw) -> List[dict]:
+    """transcribe_mel with `sections`: cut, decode the sections as files that share their owner's language, merge."""
+    n_files = len(mels)
+    if len(content_frames) != n_files:
+        raise ValueError(f"transcribe: {len(content_frames)} content_frames for {n_files} mels")
+    ladder = kw['temperatures']
+    check_supported(decoding, tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])),
+                    kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
+    if n_files == 0:
+        return []
+    W = 2 * decoding.decoder_config['num_audio_ctx']
+    fs = longform.CHUNK_LENGTH / W
+    mels = [m.to(torch.float16).contiguous() for m in mels]
+    content_frames = [int(c) for c in content_frames]
+    cuts = section_cuts(mels, content_frames, options, window=W)
+    pieces, piece_frames, owner, starts = section_mels(mels, content_frames, cuts, W)
+    parts = _transcribe_files(encoding, decoding, pieces, piece_frames, owner, **kw)
+    tk = decoding.tokenizer
+    out = []
+    for f in range(n_files):
+        mine = [i for i, o in enumerate(owner) if o == f]
+        segments = sections_mod.merge_sections([parts[i]['segments'] for i in mine], [starts[i] for i in mine], fs)
+        text = tk.decode([t for s in segments for t in s['tokens']]).strip()
+        language = parts[mine[0]]['language'] if mine else _language_without_audio(decoding)
+        out.append(dict(language=language, text=text, segments=segments,
+                        sections=[(starts[i] * fs, (starts[i] + piece_frames[i]) * fs) for i in mine]))
+    return out
+
+
+def _named_language(decoding: WhisperDecoding) -> Optional[str]:
+    if decoding.is_multilingual and decoding.options.language is not None:
+        return Tokenizer._defaults(True, decoding.options.language, None)[0]
+    return None
+
+
+def _language_without_audio(decoding: WhisperDecoding) -> Optional[str]:
+    """What a file says of its language before any window of it was heard: the named one, None until detected."""
+    return _named_language(decoding) if decoding.is_multilingual else 'en'
+
+
+def _transcribe_files(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: Sequence[torch.Tensor],
+                      content_frames: Sequence[int], owner: Optional[Sequence[int]], *, temperatures, compression_ratio_threshold,
+                      logprob_threshold, no_speech_threshold, n_rows, trace, condition_on_previous_text, initial_prompt,
+                      word_timestamps) -> List[dict]:
+    """transcribe_mel's body.  `owner`: None, or per "file" the file it is a section of: the sections of a file stand together
+    in section order and share ONE language, detected (unless named) on the first window of the first of them."""
     temperatures = tuple(float(t) for t in (temperatures if isinstance(temperatures, (tuple, list)) else [temperatures]))
     check_supported(decoding, temperatures, condition_on_previous_text, initial_prompt, word_timestamps)
     if isinstance(initial_prompt, str):
@@ -158,12 +279,10 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
         n_rows = default_rows(decoding, max(1, sum(1 for c in content_frames if c > 0)), dev, word_timestamps)
     n_group = decoding.n_group
 
-    # the language of every file: named by the options, or detected on the file's first window
+    # the language of every file: named by the options, or detected on the file's first window (of its first section)
     multilingual = decoding.is_multilingual
-    named = None
-    if multilingual and decoding.options.language is not None:
-        named = Tokenizer._defaults(True, decoding.options.language, None)[0]
-    file_language: List[Optional[str]] = [named if multilingual else 'en'] * n_files
+    named = _named_language(decoding)
+    languages = sections_mod.SectionLanguages(n_files, owner, _language_without_audio(decoding))
     default_token = tk.special_tokens[f"<|{named or 'en'}|>"] if multilingual else None
 
     win = torch.zeros((n_rows, n_mels, W), dtype=torch.float16, device=dev)
@@ -177,14 +296,14 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
         state['windows_host'] = win.cpu() if trace is not None else None
         state['detected'] = {}
         if multilingual:
-            fresh = [i for i, r in enumerate(rows) if r is not None and file_language[r[0]] is None]
+            fresh = languages.fresh(rows)
             if fresh:
                 langs, _ = decoding.detect_language(features)
                 for i in fresh:
-                    file_language[rows[i][0]] = langs[i]
+                    languages.detected(rows[i][0], langs[i])
                     state['detected'][rows[i][0]] = (i, langs[i])
-            state['languages'] = [(named or 'en') if r is None else file_language[r[0]] for r in rows]
-            state['tokens'] = [default_token if r is None else tk.special_tokens[f"<|{file_language[r[0]]}|>"] for r in rows]
+            state['languages'] = [(named or 'en') if r is None else languages.known(r[0]) for r in rows]
+            state['tokens'] = [default_token if r is None else tk.special_tokens[f"<|{languages.known(r[0])}|>"] for r in rows]
         else:
             state['languages'], state['tokens'] = ['en'] * len(rows), None
 
@@ -233,7 +352,7 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
     out = []
     for f in range(n_files):
         text = tk.decode([t for s in segments[f] for t in s['tokens']]).strip()
-        out.append(dict(language=file_language[f], text=text, segments=segments[f]))
+        out.append(dict(language=languages.of(f), text=text, segments=segments[f]))
     return out
 
 
@@ -274,6 +393,11 @@ def parse_arguments(argv=None):
     parser.add_argument('--initial_prompt', type=str, default=None, help="text in front of every file's first window: names, spelling, style")
     parser.add_argument('--word_timestamps', default=False, action='store_true',
                         help='print "start-end word (probability)" lines under every segment (cross-attention alignment + DTW on the device; greedy decoding only)')
+    parser.add_argument('--sections', default=False, action='store_true',
+                        help='cut every file where it is quietest and decode the sections side by side: one long file fills the batch '
+                             '(no text or timestamp crosses a cut; conditioning keeps its history per section)')
+    parser.add_argument('--section_seconds', type=float, default=SectionOptions.max_seconds, help='longest section (default: 30)')
+    parser.add_argument('--min_section_seconds', type=float, default=None, help='shortest section but for the last (default: half the longest)')
     return parser.parse_args(argv)
 
 
@@ -287,7 +411,8 @@ def main(args) -> List[dict]:
     temperatures = tuple(args.temperature[:1] if args.no_fallback else args.temperature)
     results = transcribe(encoding, decoding, args.input_file, temperatures=temperatures, n_rows=args.rows,
                          condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt,
-                         word_timestamps=args.word_timestamps)
+                         word_timestamps=args.word_timestamps,
+                         sections=SectionOptions(args.section_seconds, args.min_section_seconds) if args.sections else None)
     for path, result in zip(args.input_file, results):
         if len(results) > 1:
             print(f"{path} ({result['language']})")

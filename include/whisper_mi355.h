@@ -63,7 +63,8 @@ typedef struct wm_dims {
  *   8  (round 6) wm_decoder_io gains `not_alone` (appended): the caller says when other decoder steps may run beside this one
  *      (still 8, like wm_mel_windows / wm_resample) wm_decoder_io gains `row_start` (appended; NULL = as before); wm_attn_decode_self_rows
  *      (still 8: test-only entries, no existing struct or signature changed) wm_attn_self_ex, wm_attn_cross_ex
- *      (still 8: an entry only) wm_forced_probs */
+ *      (still 8: an entry only) wm_forced_probs
+ *      (still 8: entries only) wm_section_cuts, wm_section_cuts_workspace_bytes */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -469,6 +470,24 @@ int wm_mel_windows(const void* const* src, const int32_t* src_frames, const int3
  * Added under ABI 8 (an entry only; no struct changes). */
 int wm_forced_probs(const void* logits, int batch, int n_pos, int n_vocab, int64_t stride_b, int64_t stride_p, int limit,
                     const int32_t* next, int next_ld, float* out, int out_ld, wm_stream_t stream);
+/* Where to cut long files into sections that are decoded side by side (sections.py states the contract).
+ * Per file b, in integers, with F = content[b] and x = src[b] fp16 [n_mels][src_ld[b]]:
+ *   q[t] = sum_m rint(clamp(x[m][t], -16, 16) * 1024)   (half to even; a non-finite element contributes 0),   0 <= t < F
+ *   s[t] = sum_{d = -h .. h} q[clamp(t + d, 0, F - 1)]
+ *   c = 0; while F - c > hi: c = the t of [c + lo, c + hi] with the smallest s[t], the largest such t among equals; c is a cut.
+ * cuts[b * cuts_ld + i] is the i-th cut of file b for i < min(n_cuts[b], cuts_ld); n_cuts[b] is the number of cuts FOUND, which
+ * may exceed cuts_ld (nothing is written past cuts_ld: the caller compares).  src: DEVICE array of `batch` device pointers (a null
+ * entry: a file without frames); src_ld, content: DEVICE int32 arrays, 0 <= content <= src_ld (content is clamped to that range);
+ * rows may start at any 2-byte address.  total_frames: an upper bound on the sum of content; files are laid out in batch
+ * order, and a file that has frames and whose last frame lies beyond total_frames in that order is not cut and reports
+ * n_cuts = -1 (so does every later file with frames; a file without frames always reports 0).  Requires 1 <= lo <= hi, h >= 0
+ * and n_mels * (2h + 1) < 131072 (every sum fits 32 bits, so the result does not depend on any order of summation).  The workspace (wm_section_cuts_workspace_bytes, 8-byte aligned) needs
+ * no initialisation.  Asynchronous on `stream`: no allocation, no host synchronisation, capturable.
+ * Added under ABI 8 (entries only; no struct changes). */
+size_t wm_section_cuts_workspace_bytes(int batch, int64_t total_frames);
+int wm_section_cuts(const void* const* src, const int32_t* src_ld, const int32_t* content, int batch, int n_mels, int lo, int hi,
+                    int h, int32_t* cuts, int cuts_ld, int32_t* n_cuts, void* workspace, size_t workspace_bytes,
+                    int64_t total_frames, wm_stream_t stream);
 /* zeroes rows 0 and Tpad - 1 of every utterance of buf fp16 [B][Tpad][C]. */
 int wm_zero_pad_rows(void* buf, int B, int Tpad, int C, wm_stream_t stream);
 /* ids[b] = arg-max of row b of fp16 logits (first index wins ties).  The decode loop itself uses
