@@ -576,7 +576,15 @@ constexpr int CROSS_MAX_SPLIT = 16;                   // key-range splits the me
 // test_cross_attention_v_skip_*, tests/test_gpu_attn_decode_contract.py); the first block of V rows is requested before the softmax and is never skipped.  With random
 // weights (diffuse attention) nothing underflows and nothing is skipped: the bench headline cannot show this, a peaked
 // synthetic fixture and FETCH_SIZE do (profiles/r4*_pmc_vskip*).
-template <int L, bool I8 = false, int UNR_ = 0, bool SKIP = false>
+// GM (candidate groups, AttnCrossParams::G > 1; the instantiations with GM = 0 do not know the field):
+//   1  decode step (p.L == 1): an item is (head, UTTERANCE, split) and serves the utterance's G = L candidate rows a * G .. a * G + G - 1
+//      from ONE walk over K/V row a -- the candidates are laid out exactly like L tokens of one utterance (q slabs and `out` rows
+//      a * L + i), and nothing below mixes two queries (s_sc[i], mx[i], o[i]), so a row's bits are those of the ungrouped L = 1 kernel
+//      on K/V repeated G times.  Only the workspace differs: its blocks stay indexed by the ORIGINAL row (the merge kernel runs
+//      per row, L = 1).  The V-row skip asks "all 8 rows weigh zero for every query of the group": still exact.  Live utterances
+//      come from p.live_utt; a dead row of a live utterance is computed like the others (finite, unspecified).
+//   2  prefill passes (p.L > 1): the row's own item, reading K/V row b / G.
+template <int L, bool I8 = false, int UNR_ = 0, bool SKIP = false, int GM = 0>
 __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
     constexpr int DPL = I8 ? 16 : 8;                     // dims per lane
     constexpr int LPR = 64 / DPL;                        // lanes per row: 8 (fp16) / 4 (int8)
@@ -602,18 +610,20 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
     // launch is persistent and leaves wave slots on every CU to the other streams' short kernels
     // rows still decoding (p.live: count, then indices): finished utterances drop out of the stream, the items are dealt
     // over the live rows only -- the launch's cost follows the live rows (the reference stops at EOT, W/decoding.py:817-819)
-    const int n_rows = p.live ? p.live[0] : p.B;
+    const int32_t* const live = GM == 1 ? p.live_utt : p.live;
+    const int n_rows = live ? live[0] : (GM == 1 ? p.B / L : p.B);
     const int n_items = p.H * n_rows * p.nsplit;
 
     struct Item { int h, b, sp, k_begin, nkeys; const unsigned char* K; const unsigned char* V; };
     auto geometry = [&](int item) {
         Item it;
         it.h = item % p.H; it.b = (item / p.H) % n_rows; it.sp = item / (p.H * n_rows);
-        if (p.live) it.b = p.live[1 + it.b];
+        if (live) it.b = live[1 + it.b];
         it.k_begin = it.sp * per_split;
         it.nkeys = max(0, min(p.Tk, it.k_begin + per_split) - it.k_begin);
-        it.K = (const unsigned char*)p.kv + ((size_t)it.b * p.kv_bstride + ((size_t)(0 * p.H + it.h) * p.Tk) * 64) * ESZ;
-        it.V = (const unsigned char*)p.kv + ((size_t)it.b * p.kv_bstride + ((size_t)(1 * p.H + it.h) * p.Tk) * 64) * ESZ;
+        const int kvr = GM == 2 ? it.b / p.G : it.b;     // (GM == 1: it.b IS the utterance)
+        it.K = (const unsigned char*)p.kv + ((size_t)kvr * p.kv_bstride + ((size_t)(0 * p.H + it.h) * p.Tk) * 64) * ESZ;
+        it.V = (const unsigned char*)p.kv + ((size_t)kvr * p.kv_bstride + ((size_t)(1 * p.H + it.h) * p.Tk) * 64) * ESZ;
         return it;
     };
     // UNR 16-byte loads of this wave's rows r0 .. of one K or V matrix (rows past the end re-read the last row)
@@ -654,10 +664,19 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
     const Item it = geometry(item);
     const int h = it.h, b = it.b, sp = it.sp, k_begin = it.k_begin, nkeys = it.nkeys;
+    // the workspace block of query i of this item (GM == 1: row b * L + i of a call with one token per row)
+    auto ws_block = [&](int i) {
+        if constexpr (GM == 1) return p.ws + (((size_t)(b * L + i) * p.H + h) * p.nsplit + sp) * 66;
+        else return p.ws + ((((size_t)b * p.H + h) * p.nsplit + sp) * L + i) * 66;
+    };
     if (nkeys == 0) {          // empty split (only possible when nsplit > 1): neutral element
         for (int idx = tid; idx < L * 66; idx += 256) {
-            float* w = p.ws + ((((size_t)b * p.H + h) * p.nsplit + sp) * L) * 66;
-            w[idx] = (idx % 66 == 0) ? -INFINITY : 0.f;
+            if constexpr (GM == 1) {
+                ws_block(idx / 66)[idx % 66] = (idx % 66 == 0) ? -INFINITY : 0.f;
+            } else {
+                float* w = p.ws + ((((size_t)b * p.H + h) * p.nsplit + sp) * L) * 66;
+                w[idx] = (idx % 66 == 0) ? -INFINITY : 0.f;
+            }
         }
         continue;
     }
@@ -667,14 +686,15 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
     u32x4 bufA[UNR], bufB[UNR];
     issue(bufA, K, k_begin, nkeys, first);
 
-    const size_t sstride = p.part_sstride ? (size_t)p.part_sstride : (size_t)p.B * L * p.ldp;
+    const size_t sstride = p.part_sstride ? (size_t)p.part_sstride : (size_t)p.B * (GM == 1 ? 1 : L) * p.ldp;
     // ---- q: this lane's DPL dims (sub * DPL .. ) for each of the L tokens -----------------------------
     // split-K slabs + bias; the slab reads of a round are all in flight together (they are L2 hits, ~1 us each:
     // taken two at a time they were 10 % of a persistent workgroup's time per item)
     float qf[L][DPL];
     {
         constexpr int QV = DPL / 4;
-        constexpr int UQ = (8 / (L * QV)) >= 2 ? (8 / (L * QV)) : 2;        // slabs per round, even
+        constexpr int QC = L <= 4 ? L : 4;                                  // queries per round of slab reads
+        constexpr int UQ = (8 / (QC * QV)) >= 2 ? (8 / (QC * QV)) : 2;      // slabs per round, even
         const int col0 = h * 64 + sub * DPL;
         float bs[DPL];
         if (p.bias) {
@@ -693,25 +713,32 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
         for (int i = 0; i < L; ++i)
 #pragma unroll
             for (int q4 = 0; q4 < QV; ++q4) qa[i][q4] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int s0 = 0; s0 < p.ksplit; s0 += UQ) {
-            float4 a[L][QV][UQ];
+        // (more than 4 queries -- a candidate group -- take their slabs four queries at a time: 8 int8 queries at once would hold
+        // 256 registers of slab data; a query's own sums are the same either way)
 #pragma unroll
-            for (int i = 0; i < L; ++i)
+        for (int c0 = 0; c0 < L; c0 += QC)
+        for (int s0 = 0; s0 < p.ksplit; s0 += UQ) {
+            float4 a[QC][QV][UQ];
+#pragma unroll
+            for (int ic = 0; ic < QC; ++ic)
 #pragma unroll
                 for (int q4 = 0; q4 < QV; ++q4)
 #pragma unroll
                     for (int u = 0; u < UQ; ++u) {
+                        const int i = min(c0 + ic, L - 1);
                         const int sl = min(s0 + u, p.ksplit - 1);
-                        a[i][q4][u] = *(const float4*)(p.part + (size_t)(b * L + i) * p.ldp + col0 + (size_t)sl * sstride + q4 * 4);
+                        a[ic][q4][u] = *(const float4*)(p.part + (size_t)(b * L + i) * p.ldp + col0 + (size_t)sl * sstride + q4 * 4);
                     }
 #pragma unroll
-            for (int i = 0; i < L; ++i)
+            for (int ic = 0; ic < QC; ++ic)
 #pragma unroll
                 for (int q4 = 0; q4 < QV; ++q4)
 #pragma unroll
                     for (int u = 0; u < UQ; u += 2) {      // same pairing as ever: qa += (slab s + slab s+1), absent slabs add 0
+                        if (c0 + ic >= L) continue;        // (compile-time after unrolling)
+                        const int i = c0 + ic;
                         const bool ok0 = s0 + u < p.ksplit, ok1 = s0 + u + 1 < p.ksplit;
-                        const float4 x = a[i][q4][u], y = a[i][q4][u + 1];
+                        const float4 x = a[ic][q4][u], y = a[ic][q4][u + 1];
                         qa[i][q4].x += (ok0 ? x.x : 0.f) + (ok1 ? y.x : 0.f);
                         qa[i][q4].y += (ok0 ? x.y : 0.f) + (ok1 ? y.y : 0.f);
                         qa[i][q4].z += (ok0 ? x.z : 0.f) + (ok1 ? y.z : 0.f);
@@ -935,7 +962,7 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
         if (single) {
             p.out[(size_t)(b * L + i) * p.ldo + h * 64 + d] = (h16)v;
         } else {
-            float* w = p.ws + ((((size_t)b * p.H + h) * p.nsplit + sp) * L + i) * 66;
+            float* w = ws_block(i);
             w[2 + d] = v;
             if (d == 0) { w[0] = gmax[i]; w[1] = gsum[i]; }
         }
@@ -982,8 +1009,20 @@ static bool cross_unr2() {
     return v;
 }
 
+// the candidate-group forms (AttnCrossParams::G > 1): NQ queries per item
+template <int NQ, int GM>
+static void launch_cross_grouped(const AttnCrossParams& p, dim3 grid, hipStream_t stream) {
+    if (p.kv_q8_scale > 0.f) hipLaunchKernelGGL((attn_cross_kernel<NQ, true, 0, false, GM>), grid, dim3(256), 0, stream, p);
+    else if (p.skip_zero_rows && p.nsplit == 1) hipLaunchKernelGGL((attn_cross_kernel<NQ, false, 0, true, GM>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((attn_cross_kernel<NQ, false, 0, false, GM>), grid, dim3(256), 0, stream, p);
+}
+
 int launch_attn_cross(const AttnCrossParams& p, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
     WM_REQUIRE(p.L >= 1 && p.L <= MAX_L, "attn_cross: L=%d out of range [1,%d]", p.L, MAX_L);
+    const int G = p.G > 0 ? p.G : 1;             // (0: a caller that does not know the field)
+    WM_REQUIRE(p.G >= 0 && p.B % G == 0 && G * p.L <= CROSS_GROUP_MAX, "attn_cross: group size G=%d needs G >= 1, B=%d a multiple of it and G * L=%d <= %d",
+               p.G, p.B, G * p.L, CROSS_GROUP_MAX);
+    WM_REQUIRE(!(G > 1 && p.L == 1) || ((p.live == nullptr) == (p.live_utt == nullptr)), "attn_cross: a candidate group takes the live rows and the live utterances together");
     WM_REQUIRE(p.Tk >= 1 && p.Tk <= CROSS_MAX_KEYS, "attn_cross: Tk=%d out of range", p.Tk);
     WM_REQUIRE(p.nsplit >= 1 && (p.nsplit == 1 || p.ws != nullptr), "attn_cross: split needs a workspace");
     WM_REQUIRE(p.nsplit <= CROSS_MAX_SPLIT, "attn_cross: nsplit=%d exceeds %d (the merge kernel holds one partial result per register)",
@@ -1005,7 +1044,7 @@ int launch_attn_cross(const AttnCrossParams& p, hipStream_t stream, hipEvent_t e
         n_cu = v > 0 ? v : 256;
         n_cu_dev[slot].store(n_cu, std::memory_order_relaxed);
     }
-    const int n_items = p.H * p.B * p.nsplit;
+    const int n_items = p.H * (G > 1 && p.L == 1 ? p.B / G : p.B) * p.nsplit;
     // default: at most 2 workgroups per CU, and every workgroup the same number of items (3840 items on 512 workgroups
     // would be 8 for some and 7 for the rest: the launch ends with half the chip idle; 480 x 8 does not).
     // Round 3 re-measured the count with the row-split chain (WM_CROSS_PERSIST_WGS, profiles/r3n_ab_kv_wgs_*.json): 480 / 384 / 320 /
@@ -1020,7 +1059,23 @@ int launch_attn_cross(const AttnCrossParams& p, hipStream_t stream, hipEvent_t e
         persist_wgs = (n_items + per - 1) / per;
     }
     dim3 grid(persist_wgs > 0 && persist_wgs < n_items ? persist_wgs : n_items);
-    if (p.kv_q8_scale > 0.f) {                                   // int8 cross K/V (opt-in)
+    if (G > 1 && p.L == 1) {                                     // one K/V walk per utterance serves its G candidate rows
+        switch (G) {
+            case 2: launch_cross_grouped<2, 1>(p, grid, stream); break;
+            case 3: launch_cross_grouped<3, 1>(p, grid, stream); break;
+            case 4: launch_cross_grouped<4, 1>(p, grid, stream); break;
+            case 5: launch_cross_grouped<5, 1>(p, grid, stream); break;
+            case 6: launch_cross_grouped<6, 1>(p, grid, stream); break;
+            case 7: launch_cross_grouped<7, 1>(p, grid, stream); break;
+            default: launch_cross_grouped<8, 1>(p, grid, stream); break;
+        }
+    } else if (G > 1) {                                          // prefill passes: the row's own item on K/V row b / G
+        switch (p.L) {
+            case 2: launch_cross_grouped<2, 2>(p, grid, stream); break;
+            case 3: launch_cross_grouped<3, 2>(p, grid, stream); break;
+            default: launch_cross_grouped<4, 2>(p, grid, stream); break;
+        }
+    } else if (p.kv_q8_scale > 0.f) {                            // int8 cross K/V (opt-in)
         switch (p.L) {
             case 1:
                 if (ev_start && ev_stop) hipExtLaunchKernelGGL((attn_cross_kernel<1, true>), grid, dim3(256), 0, stream, ev_start, ev_stop, 0, p);

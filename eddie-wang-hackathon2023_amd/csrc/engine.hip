@@ -592,7 +592,18 @@ int cross_nsplit(int B, int H) {
     return B * H <= 160 ? 4 : 1;
 }
 
-DecWs carve_decoder(const wm_engine* e, int B, int L, void* ws) {
+// candidate groups (wm_decoder_group_io::cross_group = G > 1, one token per row): the cross-attention launch has H * B / G * nsplit items, so
+// the key range is cut for B / G utterances.  The workspace is sized for the most pieces any group size of the batch takes, so that
+// wm_decoder_workspace_bytes(batch, n_new) holds for every cross_group and the layout does not depend on it.
+int cross_nsplit_group(int B, int H, int L, int G) { return (G > 1 && L == 1) ? cross_nsplit(B / G, H) : cross_nsplit(B, H); }
+int cross_nsplit_most(int B, int H, int L) {
+    int n = cross_nsplit(B, H);
+    for (int G = 2; L == 1 && G <= CROSS_GROUP_MAX; ++G)
+        if (B % G == 0) { const int m = cross_nsplit(B / G, H); n = n > m ? n : m; }
+    return n;
+}
+
+DecWs carve_decoder(const wm_engine* e, int B, int L, void* ws, int G = 1) {
     const wm_dims& d = e->dims;
     const size_t C = d.n_text_state, M = (size_t)B * L;
     Carver c{(unsigned char*)ws, 0};
@@ -610,8 +621,8 @@ DecWs carve_decoder(const wm_engine* e, int B, int L, void* ws) {
     }
     w.part_elems = widest * M;
     w.part = c.take<float>(w.part_elems);
-    w.nsplit = cross_nsplit(B, d.n_text_head);
-    w.cross_ws = c.take<float>((size_t)B * d.n_text_head * w.nsplit * L * 66);
+    w.nsplit = cross_nsplit_group(B, d.n_text_head, L, G);
+    w.cross_ws = c.take<float>((size_t)B * d.n_text_head * cross_nsplit_most(B, d.n_text_head, L) * L * 66);
     const size_t R = M < (size_t)CHAIN_MAX_ROWS ? M : (size_t)CHAIN_MAX_ROWS;      // rows the one-launch step serves (gemv_chain.hip): every edge [rows][...]
     w.gran_x = c.take<unsigned long long>(R * (C / 2) + 8);
     w.gran_h = c.take<unsigned long long>(R * 2 * C + 8);
@@ -770,6 +781,8 @@ int chain_max_rows() {
 struct GroupStep {
     const wm_engine* e; const wm_decoder_io* io; DecWs w;
     int B, L, T, C, H, M;
+    int G = 1;                                   // candidate rows per utterance that share one cross K/V row (wm_decoder_group_io::cross_group)
+    const int32_t* live_groups = nullptr;        // ... and the utterances with a live row (beside io->live_rows)
     bool small = false;                          // the fused small-batch path (gemv_small.hip)
     bool chain = false;                          // ... with its Linears chained inside one launch (one row: gemv_chain.hip)
     int chain_wgs = 0; unsigned* chain_err = nullptr; ChainDev* chain_cd = nullptr;
@@ -802,8 +815,9 @@ struct GroupStep {
     // alone: no other group's step is issued beside this one.  The one-launch forms need their 256 workgroups resident TOGETHER (one
     // fills a CU's LDS); two such launches dispatched side by side on two streams could each get half of the chip and wait for the
     // other half until the bounded waits give up -- so only a step that runs alone takes them.
-    int init(const wm_engine* e_, const wm_decoder_io* io_, hipStream_t stream, bool alone = true) {
-        e = e_; io = io_;
+    int init(const wm_engine* e_, const wm_decoder_io* io_, hipStream_t stream, bool alone = true, int cross_group = 0,
+             const int32_t* live_groups_ = nullptr) {
+        e = e_; io = io_; live_groups = live_groups_;
         prof = &g_prof_dev[e->device >= 0 && e->device < MAX_DEVICES ? e->device : 0];
         WM_REQUIRE(io && io->tokens && io->positional_embedding && io->present && io->cross && io->logits && io->workspace,
                    "wm_decoder_step: null argument");
@@ -816,7 +830,11 @@ struct GroupStep {
         WM_REQUIRE(io->present_capacity >= T + L, "wm_decoder_step: present capacity %d < n_past + n_new = %d", io->present_capacity, T + L);
         WM_REQUIRE(!io->n_past_dev || (L == 1 && io->past), "wm_decoder_step: a device step counter needs n_new == 1 and past buffers");
         WM_REQUIRE(C == H * 64, "head size must be 64");
-        w = carve_decoder(e, B, L, io->workspace);
+        G = cross_group > 1 ? cross_group : 1;
+        WM_REQUIRE(cross_group >= 0 && B % G == 0 && G * L <= CROSS_GROUP_MAX,
+                   "wm_decoder_step_group: cross_group=%d needs batch=%d a multiple of it and cross_group * n_new=%d <= %d", cross_group, B, G * L, CROSS_GROUP_MAX);
+        WM_REQUIRE(!(G > 1 && L == 1 && io->live_rows) || live_groups, "wm_decoder_step_group: cross_group with live_rows needs live_groups (wm_step_finish_group)");
+        w = carve_decoder(e, B, L, io->workspace, G);
         WM_REQUIRE(io->workspace_bytes >= w.total, "decoder workspace too small: %zu < %zu", io->workspace_bytes, w.total);
         small = M <= small_path_max_rows();
         rows = !small && rows_path_min_rows() > 0 && M >= rows_path_min_rows() && !e->dec.empty() && gemm_rows_supports(C, e->dec[0].qkv.wcode);
@@ -1076,6 +1094,7 @@ struct GroupStep {
         p.kv_q8_scale = e->i8cross() ? Lr.cross_scale : 0.f;
         p.out = w.ctx; p.ldo = C; p.nsplit = w.nsplit; p.ws = w.cross_ws;
         p.live = io->live_rows;
+        p.G = G; p.live_utt = (G > 1 && L == 1 && io->live_rows) ? live_groups : nullptr;
         p.skip_zero_rows = g_cross_v_skip.load(std::memory_order_relaxed);
         const int slot = (L == 1) ? prof_slot(*prof, i, s) : -1;
         if (launch_attn_cross(p, s, slot >= 0 ? prof->start[slot] : nullptr, slot >= 0 ? prof->stop[slot] : nullptr)) return 2;
@@ -1145,7 +1164,7 @@ struct GroupStep {
 
 }  // namespace
 
-int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t stream_) {
+static int decoder_step(const wm_engine* e, const wm_decoder_io* io, int cross_group, const int32_t* live_groups, wm_stream_t stream_) {
     WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_step: not a decoder engine");
     hipStream_t s = (hipStream_t)stream_;
     if (io && io->n_new > DEC_CHUNK) {              // a long token block: 4-token passes over the growing cache
@@ -1166,7 +1185,7 @@ int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t str
             sub.positional_embedding = (const h16*)io->positional_embedding + (size_t)off * C;
             sub.logits = stage; sub.workspace_bytes = base;
             if (off > 0) { sub.past = (const void* const*)io->present; sub.past_capacity = io->present_capacity; }   // the cache so far lives in `present`
-            if (int rc = wm_decoder_step(e, &sub, stream_)) return rc;
+            if (int rc = decoder_step(e, &sub, cross_group, live_groups, stream_)) return rc;
             // [B, l, V] -> rows off .. off+l of the caller's [B, L, V]
             WM_CHECK_HIP(hipMemcpy2DAsync((h16*)io->logits + (size_t)off * V, (size_t)L * V * sizeof(h16), stage, (size_t)l * V * sizeof(h16),
                                           (size_t)l * V * sizeof(h16), (size_t)B, hipMemcpyDeviceToDevice, s));
@@ -1175,7 +1194,8 @@ int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t str
     }
     GroupStep g;
     // (right-aligned rows: gemv_chain.hip's copy of the self-attention knows no row_start -- such a call is never `alone`)
-    if (int rc = g.init(e, io, s, !(io && (io->not_alone || io->row_start)))) return rc;
+    // (candidate groups: neither does its copy of the cross-attention know cross_group)
+    if (int rc = g.init(e, io, s, !(io && (io->not_alone || io->row_start || cross_group > 1)), cross_group, live_groups)) return rc;
     if (g.begin(s)) return 2;
     for (int i = 0; i < e->dims.n_text_layer; ++i) {
         if (g.pre_cross(i, s)) return 2;
@@ -1183,6 +1203,13 @@ int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t str
         if (g.post_cross(i, s)) return 2;
     }
     return g.end(s);
+}
+
+int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t stream) { return decoder_step(e, io, 0, nullptr, stream); }
+
+int wm_decoder_step_group(const wm_engine* e, const wm_decoder_group_io* gio, wm_stream_t stream) {
+    WM_REQUIRE(gio, "wm_decoder_step_group: null argument");
+    return decoder_step(e, &gio->io, gio->cross_group, gio->live_groups, stream);
 }
 
 // wm_decoder_step on the launch-per-kernel path, with the cross-attention queries of the listed heads written to the tape: behind
@@ -1330,6 +1357,9 @@ int wm_step_advance(int32_t* counter, wm_stream_t stream) { return launch_step_a
 int wm_step_finish(int32_t* counter, const int32_t* done, int batch, int32_t* live, wm_stream_t stream) {
     return launch_step_finish(counter, done, batch, live, (hipStream_t)stream);
 }
+int wm_step_finish_group(int32_t* counter, const int32_t* done, int batch, int group, int32_t* live, int32_t* live_groups, wm_stream_t stream) {
+    return launch_step_finish_group(counter, done, batch, group, live, live_groups, (hipStream_t)stream);
+}
 
 // ================================================================================================ kernel-level
 int wm_gemm(const void* A, int lda, int M, int K, const void* W, int N, int w8, const void* scale,
@@ -1450,7 +1480,8 @@ int wm_attn_self_ex(const wm_attn_self_io* io, wm_stream_t stream) {
     return launch_attn_self(p, (hipStream_t)stream);
 }
 
-int wm_attn_cross_ex(const wm_attn_cross_io* io, wm_stream_t stream) {
+// the checks and the launch wm_attn_cross_ex and wm_attn_cross_group_ex share (G = 1, kvB = B: the ungrouped entry)
+static int attn_cross_ex(const wm_attn_cross_io* io, int G, const int32_t* live_utt, wm_stream_t stream) {
     WM_REQUIRE(io && io->part && io->kv && io->out, "wm_attn_cross_ex: null argument");
     WM_REQUIRE(io->B >= 1 && io->H >= 1 && io->L >= 1 && io->Tk >= 1, "wm_attn_cross_ex: bad B/L/H/Tk (%d, %d, %d, %d)", io->B, io->L, io->H, io->Tk);
     const int C = io->H * 64;
@@ -1462,6 +1493,10 @@ int wm_attn_cross_ex(const wm_attn_cross_io* io, wm_stream_t stream) {
     WM_REQUIRE(io->ldo >= C, "wm_attn_cross_ex: ldo=%d < H * 64 = %d", io->ldo, C);
     WM_REQUIRE(io->kv_bstride >= (int64_t)2 * C * io->Tk && io->kv_bstride % 16 == 0,
                "wm_attn_cross_ex: kv_bstride must be a multiple of 16, >= 2 * H * Tk * 64");
+    WM_REQUIRE(G >= 1 && io->B % G == 0 && G * io->L <= CROSS_GROUP_MAX, "wm_attn_cross_group_ex: G=%d needs G >= 1, B=%d a multiple of it, G * L=%d <= %d",
+               G, io->B, G * io->L, CROSS_GROUP_MAX);
+    WM_REQUIRE(!live_utt || (G > 1 && io->L == 1 && io->live), "wm_attn_cross_group_ex: live_utt goes with G > 1, L == 1 and a live list");
+    WM_REQUIRE(!(G > 1 && io->L == 1 && io->live) || live_utt, "wm_attn_cross_group_ex: a live list needs live_utt when G > 1 and L == 1");
     WM_REQUIRE(io->kv_q8_scale >= 0.f, "wm_attn_cross_ex: kv_q8_scale must not be negative");
     WM_REQUIRE(io->nsplit >= 1 && (io->nsplit == 1 || io->ws), "wm_attn_cross_ex: nsplit=%d needs a workspace", io->nsplit);
     AttnCrossParams p{};
@@ -1470,7 +1505,19 @@ int wm_attn_cross_ex(const wm_attn_cross_io* io, wm_stream_t stream) {
     p.kv_q8_scale = io->kv_q8_scale;
     p.out = (h16*)io->out; p.ldo = io->ldo; p.nsplit = io->nsplit; p.ws = io->ws; p.live = io->live;
     p.skip_zero_rows = io->skip_zero_rows ? 1 : 0;
+    p.G = G; p.live_utt = live_utt;
     return launch_attn_cross(p, (hipStream_t)stream);
+}
+
+int wm_attn_cross_ex(const wm_attn_cross_io* io, wm_stream_t stream) { return attn_cross_ex(io, 1, nullptr, stream); }
+
+int wm_attn_cross_group_ex(const wm_attn_cross_group_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io, "wm_attn_cross_group_ex: null argument");
+    wm_attn_cross_io c{};
+    c.part = io->part; c.ksplit = io->ksplit; c.ldp = io->ldp; c.part_sstride = io->part_sstride; c.bias = io->bias;
+    c.B = io->B; c.L = io->L; c.H = io->H; c.Tk = io->Tk; c.kv = io->kv; c.kv_bstride = io->kv_bstride; c.kv_q8_scale = io->kv_q8_scale;
+    c.out = io->out; c.ldo = io->ldo; c.nsplit = io->nsplit; c.ws = io->ws; c.live = io->live; c.skip_zero_rows = io->skip_zero_rows;
+    return attn_cross_ex(&c, io->G, io->live_utt, stream);
 }
 
 int wm_embed(const int32_t* tokens, int tokens_ld, int M, int L, const void* emb_tiles, int C, const void* pos,

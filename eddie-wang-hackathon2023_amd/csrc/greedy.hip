@@ -223,6 +223,37 @@ int launch_step_finish(int32_t* counter, const int32_t* done, int B, int32_t* li
     return 0;
 }
 
+// the same, and the list of the UTTERANCES (groups of G consecutive rows) that still have a live row
+__global__ __launch_bounds__(1024) void step_finish_group_kernel(int32_t* counter, const int32_t* done, int B, int G, int32_t* live, int32_t* live_utt) {
+    __shared__ int s_cnt[16];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (tid == 0 && counter) *counter += 1;
+    auto compact = [&](bool alive, int32_t* list) {
+        const unsigned long long mask = __ballot(alive);
+        const int before = __popcll(mask & ((1ull << lane) - 1ull));
+        __syncthreads();                      // (the counts of the pass before have been read)
+        if (lane == 0) s_cnt[wid] = __popcll(mask);
+        __syncthreads();
+        int base = 0, total = 0;
+        for (int w = 0; w < 16; ++w) { if (w < wid) base += s_cnt[w]; total += s_cnt[w]; }
+        if (alive) list[1 + base + before] = tid;
+        if (tid == 0) list[0] = total;
+    };
+    compact(tid < B && done[tid] == 0, live);
+    bool any = false;
+    if (tid < B / G)
+        for (int j = 0; j < G; ++j) any |= done[tid * G + j] == 0;
+    compact(any, live_utt);
+}
+
+int launch_step_finish_group(int32_t* counter, const int32_t* done, int B, int G, int32_t* live, int32_t* live_utt, hipStream_t stream) {
+    WM_REQUIRE(done && live && live_utt && B >= 1 && B <= 1024, "step_finish_group: null argument or batch %d outside [1, 1024]", B);
+    WM_REQUIRE(G >= 1 && B % G == 0, "step_finish_group: batch %d is not a multiple of the group size %d", B, G);
+    hipLaunchKernelGGL(step_finish_group_kernel, dim3(1), dim3(1024), 0, stream, counter, done, B, G, live, live_utt);
+    WM_LAUNCH_CHECK(stream, "step_finish_group");
+    return 0;
+}
+
 int launch_step_advance(int32_t* counter, hipStream_t stream) {
     WM_REQUIRE(counter, "step_advance: null counter");
     hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, stream, counter);

@@ -231,7 +231,16 @@ struct AttnCrossParams {
     float* ws;                               // [B*H*nsplit][L][66] partial (m, l, o[64]) when nsplit > 1
     const int32_t* live;                     // optional [1 + B]: count, then the rows to process (others are skipped)
     int skip_zero_rows;                      // fp16 K/V, nsplit == 1: V rows whose probabilities all round to fp16 zero are not fetched (exact)
+    // candidate groups (0 / 1: none): rows a * G .. a * G + G - 1 read K/V row a of kv [B / G][2][H][Tk][64]; B % G == 0, G * L <= 8.
+    // L == 1: one item per (head, utterance, split) serves the G queries from one K/V stream, bit-identical per row with the ungrouped
+    // call on K/V repeated G times; L > 1: the row's own item reads K/V row b / G.  ws blocks stay indexed by the original row.
+    int G;
+    // G > 1, L == 1: optional [1 + B / G]: count, then the utterances with a live row (launch_step_finish_group writes it beside
+    // `live`); given together with `live` or not at all.  An utterance that is not listed is not read; a dead row of a listed one gets
+    // finite, unspecified output
+    const int32_t* live_utt;
 };
+constexpr int CROSS_GROUP_MAX = 8;           // queries one K/V walk serves (= BEAM_MAX, beam.hip)
 // (bit-identical with it on or off: test_cross_attention_v_skip_*, and at the key-range edges tests/test_gpu_attn_decode_contract.py)
 constexpr int CROSS_V_SKIP_DEFAULT = 1;      // measured: profiles/r4e_* (diffuse attention: no slower; peaked: FETCH_SIZE falls with the skipped rows)
 int launch_attn_cross(const AttnCrossParams& p, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
@@ -257,6 +266,8 @@ struct GreedyParams {
 int launch_greedy(const GreedyParams& p, hipStream_t stream);
 int launch_step_advance(int32_t* counter, hipStream_t stream);
 int launch_step_finish(int32_t* counter, const int32_t* done, int B, int32_t* live, hipStream_t stream);
+// ... and, for candidate groups of G rows (B % G == 0), the utterances with a live row: live_utt[0] = their number, then their indices, ascending
+int launch_step_finish_group(int32_t* counter, const int32_t* done, int B, int G, int32_t* live, int32_t* live_utt, hipStream_t stream);
 int launch_argmax(const h16* logits, long ld_row, int B, int V, int32_t* ids, hipStream_t stream);
 
 // ---------------------------------------------------------------- beam.hip

@@ -207,6 +207,32 @@ def check_decoding_options(options: DecodingOptions) -> None:
         raise ValueError("patience requires beam_size to be given")
 
 
+def candidate_mode(options: DecodingOptions, fallback_best_of: Optional[int], temperature: float) -> Tuple[str, int]:
+    """How one main_loop call at `temperature` decodes, and how many candidates per utterance it ranks: ("beam", beam_size) or
+    ("sample", n).  Upstream's decode_with_fallback drops beam_size / patience above temperature 0 and best_of at 0; an instance
+    built with `fallback_best_of = M` follows it: beam search at 0, M independent samples above.  Without it the instance's own
+    options hold at every temperature (beam search, or best_of / one sample)."""
+    if options.beam_size is not None:
+        if fallback_best_of is not None and temperature > 0:
+            return "sample", int(fallback_best_of)
+        return "beam", int(options.beam_size)
+    return "sample", int(options.best_of or 1)
+
+
+def check_candidate_options(options: DecodingOptions, shared_cross_kv: bool, fallback_best_of: Optional[int]) -> None:
+    """The combinations `shared_cross_kv` / `fallback_best_of` take (WhisperDecoding)."""
+    if fallback_best_of is None:
+        return
+    if options.best_of is not None:
+        raise ValueError("fallback_best_of and best_of can't be given together (best_of alone samples at every temperature)")
+    if options.beam_size is None:
+        raise ValueError("fallback_best_of needs beam_size: it is the number of samples a beam-search instance draws above temperature 0")
+    if not shared_cross_kv:
+        raise ValueError("fallback_best_of needs shared_cross_kv=True (the candidates of both modes share one copy of the cross K/V)")
+    if not 1 <= int(fallback_best_of) <= options.beam_size:
+        raise ValueError(f"fallback_best_of {fallback_best_of} outside 1..beam_size = {options.beam_size} (the rows are n_audio x beam_size in both modes)")
+
+
 class BeamSearchDecoder:
     """Beam search with the semantics of upstream Whisper's BeamSearchDecoder, in torch on the host: the literal statement of
     the contract that the device step (csrc/beam.hip, wm_beam_io in include/whisper_mi355.h) implements.
@@ -350,8 +376,15 @@ def right_aligned_rows(prompts: Sequence[Sequence[int]], sot_sequence: Sequence[
 
 class WhisperDecoding:
     def __init__(self, engine_dir, only_torch: bool = False, vocab_path: Optional[str] = None,
-                 options: Optional[DecodingOptions] = None, row_prompts: bool = False):
-        """`row_prompts`: every utterance of a main_loop call may carry a prompt of its own (`set_prompts`: the previous text of
+                 options: Optional[DecodingOptions] = None, row_prompts: bool = False, shared_cross_kv: bool = False,
+                 fallback_best_of: Optional[int] = None):
+        """`shared_cross_kv` (opt-in): the n_group candidates of an utterance (beams, best_of samples) read ONE copy of its
+        cross-attention K/V (wm_decoder_group_io::cross_group) instead of a copy each: the cross K/V are projected once from the
+        un-repeated features, held once per utterance and streamed once per utterance and token step.  Device loop only; not
+        with `cu_partition`.  `fallback_best_of = M` (with beam_size = K >= M and shared_cross_kv): main_loop(temperature = t)
+        runs beam search at t == 0 and M independent samples per utterance at t > 0 (`candidate_mode`), on the same n_audio x K
+        rows, buffers and cross K/V -- upstream's decode_with_fallback.
+        `row_prompts`: every utterance of a main_loop call may carry a prompt of its own (`set_prompts`: the previous text of
         long-form transcription, names and spellings).  The rows are right-aligned (`right_aligned_rows`): all of them are
         L0 = n_text_ctx // 2 + len(sot_sequence) tokens long and `sample_begin`, `sot_index`, the buffers and the captured graphs
         are fixed at construction; only where a row begins differs.  The price is the room for sampling: the effective
@@ -378,6 +411,10 @@ class WhisperDecoding:
         self.sot_index = self.initial_tokens.index(self.tokenizer.sot)
         self.options = options or DecodingOptions()
         check_decoding_options(self.options)
+
+        check_candidate_options(self.options, bool(shared_cross_kv), fallback_best_of)
+        self.shared_cross_kv = bool(shared_cross_kv)
+        self.fallback_best_of = None if fallback_best_of is None else int(fallback_best_of)
 
         self.n_group = self.options.beam_size or self.options.best_of or 1
         self.sample_len: int = self.options.sample_len or self.decoder_config['num_text_ctx'] // 2
@@ -674,6 +711,11 @@ class WhisperDecoding:
                     audio_features.wm_generation = gen      # of one clip would be projected twice, once per view)
             n_audio, dev = audio_features.shape[0], audio_features.device
             cfg = self.decoder_config
+            if self._cross_group() > 1 and audio_features.is_cuda:
+                # shared cross K/V: the pass runs over the n_audio utterances themselves (group 1), on the cross K/V and the first
+                # n_audio cache rows of the buffer set main_loop will use -- nothing is repeated, nothing projected twice
+                self._require_device_loop("detect_language")
+                return self._detect_language_rows(audio_features, single, _retry)
             if self.n_group > 1 and self.device_sampling and audio_features.is_cuda:
                 # best_of / beam candidates: main_loop decodes n_audio x n_group rows.  The state keeps ONE buffer set at a time, so a
                 # language pass over n_audio rows would free and re-allocate the caches, the cross K/V buffers and the graphs on every
@@ -689,6 +731,17 @@ class WhisperDecoding:
                 return languages, language_probs
             return self._detect_language_rows(audio_features, single, _retry)
         return languages, language_probs
+
+    def _cross_group(self) -> int:
+        """Candidate rows that share one cross K/V row (wm_decoder_group_io::cross_group): n_group on a `shared_cross_kv` instance, else 1."""
+        return self.n_group if self.shared_cross_kv else 1
+
+    def _require_device_loop(self, what: str) -> None:
+        if self.shared_cross_kv and self.n_group > 1:
+            if not self.device_sampling:
+                raise ValueError(f"{what}: shared_cross_kv needs the device loop (device_sampling = False is the literal host loop, which repeats the features)")
+            if self.cu_partition:
+                raise ValueError(f"{what}: shared_cross_kv is not supported by the CU-partitioned schedule (cu_partition = True)")
 
     def _candidate_rows(self, audio_features):
         """The audio features with every clip repeated n_group times (best_of / beam candidates share their utterance's audio: the
@@ -708,8 +761,8 @@ class WhisperDecoding:
         languages, language_probs = None, None
         n_audio, dev = audio_features.shape[0], audio_features.device
         cfg = self.decoder_config
-        st = self._fast_state(n_audio, dev)
-        n_micro_, bounds_ = self._groups(n_audio)   # groups of up to eight rows stepped one at a time may run as ONE launch per step
+        st = self._fast_state(n_audio * self._cross_group(), dev)     # (shared cross K/V: the candidates' buffer set, its first n_audio rows)
+        n_micro_, bounds_ = self._groups(n_audio, unit=1)   # groups of up to eight rows stepped one at a time may run as ONE launch per step
         one_row = (n_micro_ == 1 or self.lang_id_sequential) and not self.force_not_alone and any(hi - lo <= 8 for lo, hi in bounds_)
         if one_row and native.chain_status()["error_pending"]:                  # (a peek at a host word: no synchronisation)
             self._chain_gave_up("found before the language pass", foreign=True)  # somebody else's give-up: said loudly, acknowledged, not ours to repeat
@@ -717,7 +770,7 @@ class WhisperDecoding:
         if 'lang_logits' not in st:
             st['lang_logits'] = torch.empty((n_audio, 1, cfg['vocab_size']), dtype=torch.float16, device=dev)
             st['sot'] = torch.full((n_audio, 1), self.tokenizer.sot, dtype=torch.int32, device=dev)
-        n_micro, bounds = self._groups(n_audio)
+        n_micro, bounds = self._groups(n_audio, unit=1)
         main = torch.cuda.current_stream()
         streams = self._group_streams(n_micro, dev)
         cap = cfg['num_text_ctx']
@@ -827,57 +880,76 @@ class WhisperDecoding:
             raise ValueError(f"{what}: an instance built with row_prompts=True decodes through the device loop only "
                              "(main_loop with features on the GPU, device_sampling on)")
 
-    def _host_step(self, i, logits, tokens, sum_logprobs, no_speech_probs):
+    def _host_call(self, temperature, n_rows):
+        """What a host loop's call at `temperature` decodes with (`_call_decoder`), and the rows it keeps closed: in a sampling call of
+        a beam instance (`fallback_best_of`) candidates j >= fallback_best_of of every utterance end before their first token."""
+        decoder, n_cand = self._call_decoder(temperature)
+        closed = None
+        if n_cand < self.n_group:
+            closed = (torch.arange(n_rows) % self.n_group) >= n_cand
+        return decoder, closed
+
+    def _host_step(self, i, logits, tokens, sum_logprobs, no_speech_probs, decoder=None, closed=None):
         if i == 0 and self.tokenizer.no_speech is not None:       # save no_speech_probs
             probs_at_sot = logits[:, self.sot_index].float().softmax(dim=-1)
             no_speech_probs[:] = probs_at_sot[:, self.tokenizer.no_speech].tolist()
         logits = logits[:, -1]
         for logit_filter in self.logit_filters:
             logit_filter.apply(logits, tokens)
-        out = self.decoder.update(tokens, logits, sum_logprobs)
+        out = (decoder or self.decoder).update(tokens, logits, sum_logprobs)
+        if closed is not None:          # closed rows: EOT from their first token on, nothing booked (the device loop's row_limit = 0)
+            new_tokens = out[0]
+            new_tokens[closed.to(new_tokens.device), -1] = self.tokenizer.eot
+            sum_logprobs[closed.to(sum_logprobs.device)] = 0
+            out = (new_tokens, bool((new_tokens[:, -1] == self.tokenizer.eot).all()), *out[2:])
         return out if len(out) == 3 else (*out, None)       # (tokens, completed, source rows of a beam step or None)
 
-    def main_loop_reference(self, audio_features):
+    def main_loop_reference(self, audio_features, temperature: Optional[float] = None):
         """The reference's loop verbatim in structure (W/decoding.py:785-821): one `decode()` per token,
-        host-side filters, concat KV."""
+        host-side filters, concat KV.  `temperature`: this call's (an instance with `fallback_best_of` samples above 0,
+        `candidate_mode`; any other instance decodes with its own decoder whatever is passed)."""
         self._refuse_row_prompts("main_loop_reference")
         tokens = self._initial_token_rows(audio_features.shape[0], audio_features.device)
         n_batch = tokens.shape[0]
+        decoder, closed = self._host_call(temperature, n_batch)
         sum_logprobs: Tensor = torch.zeros(n_batch, device=audio_features.device)
         no_speech_probs = [np.nan] * n_batch
         past_key_value = None
         if self.n_group > 1:        # best_of / beam candidates share their utterance's audio (upstream Whisper repeats it too)
             audio_features = audio_features.repeat_interleave(self.n_group, dim=0)
         cross = self.xa2cross_key_value(audio_features)
-        if self.beam:
+        if self.beam and decoder is self.decoder:
             self.decoder.reset(audio_features.shape[0] // self.n_group)
         for i in range(self.sample_len):
             feed = tokens if tokens.shape[-1] <= self.initial_token_length else tokens[:, -1:]
             logits, past_key_value = self.decode(feed, cross, past_key_value)
-            tokens, completed, source = self._host_step(i, logits, tokens, sum_logprobs, no_speech_probs)
+            tokens, completed, source = self._host_step(i, logits, tokens, sum_logprobs, no_speech_probs, decoder, closed)
             if source is not None and past_key_value is not None:       # the caches follow their beams
                 past_key_value = [kv[source.to(kv.device)] for kv in past_key_value]
             if completed or tokens.shape[-1] > self.decoder_config['num_text_ctx']:
                 break
         return tokens, sum_logprobs, no_speech_probs
 
-    def torch_main_loop(self, model, audio_features):
-        """PyTorch path (W/decoding.py:743-783): `model.decoder(tokens, xa, kv_cache=)` with hooks."""
+    def torch_main_loop(self, model, audio_features, temperature: Optional[float] = None):
+        """PyTorch path (W/decoding.py:743-783): `model.decoder(tokens, xa, kv_cache=)` with hooks.  `temperature`: as
+        main_loop_reference."""
         self._refuse_row_prompts("torch_main_loop")
         with torch.no_grad():
             tokens = self._initial_token_rows(audio_features.shape[0], audio_features.device)
             n_batch = tokens.shape[0]
             sum_logprobs: Tensor = torch.zeros(n_batch, device=audio_features.device)
             no_speech_probs = [np.nan] * n_batch
+            decoder, closed = self._host_call(temperature, n_batch)
             if self.beam:
-                self.decoder.reset(audio_features.shape[0])
+                if decoder is self.decoder:
+                    self.decoder.reset(audio_features.shape[0])
                 audio_features = audio_features.repeat_interleave(self.n_group, dim=0)     # beams share their utterance's audio
             for i in range(self.sample_len):
                 if not self.kv_cache:
                     self.kv_cache, self.hooks = model.install_kv_cache_hooks()
                 feed = tokens if tokens.shape[-1] <= self.initial_token_length else tokens[:, -1:]
                 logits = model.decoder(feed, audio_features, kv_cache=self.kv_cache)
-                tokens, completed, source = self._host_step(i, logits, tokens, sum_logprobs, no_speech_probs)
+                tokens, completed, source = self._host_step(i, logits, tokens, sum_logprobs, no_speech_probs, decoder, closed)
                 if source is not None:                                   # the cached keys / values follow their beams (every per-row entry, as upstream)
                     for key, value in list(self.kv_cache.items()):
                         if torch.is_tensor(value) and value.shape[0] == source.shape[0]:
@@ -926,7 +998,7 @@ class WhisperDecoding:
         blank = list(tk.blank_tokens()) + [tk.eot] if self.options.suppress_blank else []
         st = dict(
             kv=[torch.zeros((n_batch, 2, n_head, cap, 64), dtype=kv_dtype, device=device) for _ in range(n_layer)],
-            cross=[torch.empty((n_batch, 2, n_head, cfg['num_audio_ctx'], 64),
+            cross=[torch.empty((n_batch // self._cross_group(), 2, n_head, cfg['num_audio_ctx'], 64),
                                dtype=torch.int8 if self.use_int8_cross_kv else torch.float16, device=device)
                    for _ in range(n_layer)],
             cross_key=None, cross_xa=None, graphs={}, counters={},
@@ -944,6 +1016,12 @@ class WhisperDecoding:
             suppress=torch.tensor(suppress or [0], dtype=torch.int32, device=device), n_suppress=len(suppress),
             blank=torch.tensor(blank or [0], dtype=torch.int32, device=device), n_blank=len(blank),
         )
+        if self._cross_group() > 1:
+            # shared cross K/V: the prefill runs on ONE row per utterance (the candidates begin alike); its logits, and the first slot of
+            # every utterance, before they are copied to the candidates' rows (_main_loop)
+            n_utt = n_batch // self._cross_group()
+            st.update(logits_u=torch.empty((n_utt, self.initial_token_length, V), dtype=torch.float16, device=device),
+                      row_start_u=torch.zeros(n_utt, dtype=torch.int32, device=device) if self.row_prompts else None)
         if self.beam:
             # the beam step's outputs: parents, the pool of finished candidates per utterance, the proposals between its two launches
             K, MC = self.decoder.beam_size, self.decoder.max_candidates
@@ -970,7 +1048,10 @@ class WhisperDecoding:
         n_layer, n_head, cap, V = cfg['num_layers'], cfg['num_heads'], cfg['num_text_ctx'], cfg['vocab_size']
         kv = 2 * n_head * cap * 64 * (1 if self.use_int8_kv_cache else 2)
         cross = 2 * n_head * cfg['num_audio_ctx'] * 64 * (1 if self.use_int8_cross_kv else 2)
+        cross = -(-cross // self._cross_group())        # (shared_cross_kv: one copy per utterance, a row's share of it)
         per_row = n_layer * (kv + cross) + (cap + 1) * 4 + self.initial_token_length * V * 2 + 64
+        if self._cross_group() > 1:        # ... and of its utterance's prefill logits (one row per utterance is prefilled)
+            per_row += -(-self.initial_token_length * V * 2 // self._cross_group())
         if self.beam:       # parent + proposals per row, and the row's share of its utterance's pool (tokens, score, length) and counters
             K, MC = self.decoder.beam_size, self.decoder.max_candidates
             per_row += 4 + (K + 1) * 8 + -(-(MC * ((cap + 1) * 4 + 8) + 8) // K)
@@ -1013,7 +1094,7 @@ class WhisperDecoding:
             self._partition = (light, heavy)
         return self._partition[0][:n], self._partition[1]
 
-    def _groups(self, n_batch):
+    def _groups(self, n_batch, unit=None):
         # three groups from 128 utterances up (two chains of short kernels hide under the third group's K/V stream;
         # four concurrent chains are slower again: 18.1 / 28.0 ms per step at B = 384), two from 13 (round 6: 14 utterances 2.29 against
         # 2.39 ms per token step, 12: 2.15 either way, 10: 2.05 / 2.08; rounds 1-5: from 16), else one
@@ -1022,7 +1103,9 @@ class WhisperDecoding:
         else:
             n_micro = self.micro_batches if n_batch >= 4 * self.micro_batches else 1
         # the beams of an utterance stay in one group (the beam step and the cache reorder work per utterance): cut in whole utterances
-        unit = self.n_group if self.beam else 1
+        # (so do the candidates that share a cross K/V row: the launch reads row b / n_group of the group's slice)
+        if unit is None:
+            unit = self.n_group if (self.beam or self.shared_cross_kv) else 1
         n_units = n_batch // unit
         n_micro = max(1, min(n_micro, n_units))
         return n_micro, [(g * n_units // n_micro * unit, (g + 1) * n_units // n_micro * unit) for g in range(n_micro)]
@@ -1032,7 +1115,7 @@ class WhisperDecoding:
         utterance groups (contiguous slices of the batch, `_groups`) like cards, so that every group holds short and long
         rows alike.  All groups then shrink together as rows finish -- their K/V streams and chains keep overlapping --
         instead of the group of the longest clips running on alone.  `batch[i] = sorted_batch[order[i]]`."""
-        unit = self.n_group if self.beam else 1        # (beam search: the groups are cut over the clips' beam rows, in whole clips)
+        unit = self.n_group if (self.beam or self.shared_cross_kv) else 1        # (beam search, shared cross K/V: the groups are cut over the clips' candidate rows, in whole clips)
         n_micro, bounds = self._groups(n_batch * unit)
         bounds = [(lo // unit, hi // unit) for lo, hi in bounds]
         room = [hi - lo for lo, hi in bounds]
@@ -1107,6 +1190,19 @@ class WhisperDecoding:
         live[0] = hi - lo
         live[1:] = torch.arange(hi - lo, dtype=torch.int32, device=live.device)
         return live
+
+    def _live_groups(self, st, n_micro, slot, lo, hi):
+        """... and, for candidates that share a cross K/V row, the group's list of utterances with a live row (int32 [1 + n / G]),
+        reset likewise; wm_step_finish_group rebuilds both."""
+        G = self._cross_group()
+        key = (n_micro, slot, 'utterances')
+        n = (hi - lo) // G
+        if key not in st['live']:
+            st['live'][key] = torch.empty(1 + n, dtype=torch.int32, device=st['done'].device)
+        lu = st['live'][key]
+        lu[0] = n
+        lu[1:] = torch.arange(n, dtype=torch.int32, device=lu.device)
+        return lu
 
     def _greedy(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None, temperature=None):
         """Fused logit rules + arg-max + append for utterances [lo, hi) of the batch state `st`."""
@@ -1192,8 +1288,14 @@ class WhisperDecoding:
         finished is no longer stepped (`skip_finished_rows`): the loop's cost follows the live rows."""
         features_in = audio_features
         temp = float(self.options.temperature if temperature is None else temperature)
+        mode, n_cand = candidate_mode(self.options, self.fallback_best_of, temp)
+        beam = self.beam and mode == "beam"                 # this call's decoder (fallback_best_of: samples above temperature 0)
+        G = self._cross_group()
+        self._require_device_loop("main_loop")
+        if G > 1 and not audio_features.is_cuda:
+            raise ValueError("main_loop: shared_cross_kv needs the device loop (features on the GPU)")
         if temp != self.options.temperature:
-            if self.beam or self.n_group != 1:
+            if (self.beam or self.n_group != 1) and self.fallback_best_of is None:
                 raise ValueError("a per-call temperature is not supported with beam_size / best_of: they decode at the instance's temperature")
             if not self.device_sampling or not audio_features.is_cuda:
                 raise ValueError("a per-call temperature needs the device loop (device_sampling on, features on the GPU)")
@@ -1203,12 +1305,12 @@ class WhisperDecoding:
             # (or tensors that are not on the GPU) keeps the literal host loop: torch's generator, the draws the goldens hold.
             if not self.device_sampling or not audio_features.is_cuda:
                 return self.main_loop_reference(audio_features)
-            if self.n_group > 1:      # candidates share their utterance's audio: the reference repeats the features too (:538-539 of this file)
+            if self.n_group > 1 and G == 1:      # candidates share their utterance's audio: the reference repeats the features too (:538-539 of this file)
                 audio_features = self._candidate_rows(audio_features)
         dev = audio_features.device
-        tokens0 = self._initial_token_rows(audio_features.shape[0] // self.n_group, dev)
+        tokens0 = self._initial_token_rows(audio_features.shape[0] * G // self.n_group, dev)
         n_batch, L0 = tokens0.shape
-        assert n_batch == audio_features.shape[0]
+        assert n_batch == audio_features.shape[0] * G
         cfg = self.decoder_config
         V, cap = cfg['vocab_size'], cfg['num_text_ctx']
         st = self._fast_state(n_batch, dev)
@@ -1234,6 +1336,10 @@ class WhisperDecoding:
             st['row_limit'].copy_(row_limit)
         else:
             st['row_limit'].fill_(1 << 30)
+        if n_cand < self.n_group:
+            # a sampling call of a beam instance: candidates j >= n_cand of every utterance are closed before their first token (EOT,
+            # nothing booked): they drop out of the kernels with the first live list and never reach the ranker (post_process)
+            st['row_limit'].view(-1, self.n_group)[:, n_cand:] = 0
         n_micro, bounds = self._groups(n_batch)
         if self.cu_partition and n_micro > 1 and self.beam:
             raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
@@ -1241,6 +1347,8 @@ class WhisperDecoding:
             raise ValueError("row_prompts is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
         if self.row_prompts:
             st['row_start'].copy_(self._row_starts)
+            if G > 1:
+                st['row_start_u'].copy_(self._row_starts[::G])
         if self.cu_partition and n_micro > 1 and self.decoder_session.qkv_amax is None and row_limit is None and temp == self.options.temperature:
             return self._main_loop_partitioned(audio_features, st, cross, L0, n_micro, bounds, ignore_eot)
         use_live = bool(self.skip_finished_rows) and not ignore_eot and max(hi - lo for lo, hi in bounds) <= 1024
@@ -1250,7 +1358,8 @@ class WhisperDecoding:
         groups = []
         for g, (lo, hi) in enumerate(bounds):
             groups.append(dict(lo=lo, hi=hi, stream=streams[g].cuda_stream, slot=g, active=True,
-                               kv=[t[lo:hi] for t in st['kv']], cross=[t[lo:hi] for t in cross],
+                               kv=[t[lo:hi] for t in st['kv']], cross=[t[lo // G:hi // G] for t in cross],
+                               live_groups=self._live_groups(st, n_micro, g, lo, hi) if use_live and G > 1 else None,
                                logits=st['logits'][lo:hi], tokens=st['tokens'][lo:hi], done=st['done'][lo:hi],
                                live=self._live_list(st, n_micro, g, lo, hi) if use_live else None,
                                row_start=st['row_start'][lo:hi] if self.row_prompts else None))
@@ -1271,7 +1380,10 @@ class WhisperDecoding:
         def finish_step(gr, counter):
             # end of a group's step: advance its device step counter (graph replay) and, with per-row completion,
             # rebuild its list of live rows from the flags the greedy kernel has just updated
-            if gr['live'] is not None:
+            if gr['live'] is not None and gr['live_groups'] is not None:
+                native.check(lib.wm_step_finish_group(counter.data_ptr() if counter is not None else None, gr['done'].data_ptr(), gr['hi'] - gr['lo'], G,
+                                                      gr['live'].data_ptr(), gr['live_groups'].data_ptr(), gr['stream']), "wm_step_finish_group")
+            elif gr['live'] is not None:
                 native.check(lib.wm_step_finish(counter.data_ptr() if counter is not None else None, gr['done'].data_ptr(),
                                                 gr['hi'] - gr['lo'], gr['live'].data_ptr(), gr['stream']), "wm_step_finish")
             elif counter is not None:
@@ -1279,12 +1391,14 @@ class WhisperDecoding:
 
         def token_step(gr, logits_ptr, row_stride, cur_len, sm, n_past_dev=None):
             # what follows a group's decoder launch: the fused greedy step, or the beam step and the cache reorder
-            if self.beam:
+            if beam:
                 self._beam(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, gr['kv_table'], ignore_eot, n_past_dev=n_past_dev)
             else:
                 self._greedy(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, n_past_dev=n_past_dev, temperature=temp)
 
-        bkey = ('beam', bool(ignore_eot)) if self.beam else ()         # (ignore_eot is an argument of the captured beam step)
+        bkey = ('beam', bool(ignore_eot)) if beam else ()         # (ignore_eot is an argument of the captured beam step)
+        if G > 1:
+            bkey += (('cross_group', G),)
         if temp != self.options.temperature:
             bkey += (('temperature', temp),)                           # (so is the temperature: a per-call one has graphs of its own)
         last_issued = None
@@ -1306,8 +1420,23 @@ class WhisperDecoding:
                     pkey = (n_micro, slot, use_live, 'prefill', L0, shared) + bkey
 
                     def issue_prefill(gr=gr, lo=lo, hi=hi, sm=sm, slot=slot):
-                        sess.decoder_step(gr['tokens'][:, :L0], pos[0:L0], gr['cross'], None, cap, gr['kv'], cap,
-                                          gr['logits'], 0, sm, slot=slot, live_rows=gr['live'], not_alone=shared, row_start=gr['row_start'])
+                        if G > 1:
+                            # shared cross K/V: the candidates of an utterance begin with the same tokens over the same audio, so ONE row
+                            # per utterance is prefilled (group 1, on the utterances' cross K/V and the group's first cache rows: what
+                            # each candidate's row would compute) and its cache slots and logits are copied to the G candidates
+                            a_lo, a_hi = lo // G, hi // G
+                            n_u = a_hi - a_lo
+                            with torch.cuda.stream(streams[slot]):
+                                sess.decoder_step(st['tokens'][lo:hi:G, :L0], pos[0:L0], gr['cross'], None, cap, [t[:n_u] for t in gr['kv']], cap,
+                                                  st['logits_u'][a_lo:a_hi], 0, sm, slot=slot, not_alone=shared,
+                                                  row_start=st['row_start_u'][a_lo:a_hi] if self.row_prompts else None)
+                                for t in gr['kv']:
+                                    first = t[:n_u, :, :, :L0].clone()
+                                    t.view(n_u, G, *t.shape[1:])[:, :, :, :, :L0] = first[:, None]
+                                gr['logits'].view(n_u, G, L0, V)[:] = st['logits_u'][a_lo:a_hi, None]
+                        else:
+                            sess.decoder_step(gr['tokens'][:, :L0], pos[0:L0], gr['cross'], None, cap, gr['kv'], cap,
+                                              gr['logits'], 0, sm, slot=slot, live_rows=gr['live'], not_alone=shared, row_start=gr['row_start'])
                         token_step(gr, gr['logits'].data_ptr() + (L0 - 1) * V * 2, L0 * V, L0, sm)
                         finish_step(gr, None)
                     if use_graph and self.graph_prefill and pkey in st['graphs']:
@@ -1328,7 +1457,7 @@ class WhisperDecoding:
                 else:
                     sess.decoder_step(gr['tokens'][:, cur - 1:cur], pos[cur - 1:cur], gr['cross'], gr['kv'], cap,
                                       gr['kv'], cap, gr['logits'], cur - 1, sm, slot=slot, live_rows=gr['live'], not_alone=shared,
-                                      row_start=gr['row_start'])
+                                      row_start=gr['row_start'], cross_group=G, live_groups=gr['live_groups'])
                     token_step(gr, gr['logits'].data_ptr(), V, cur, sm)
                     finish_step(gr, None)
                     if use_graph:
@@ -1348,7 +1477,7 @@ class WhisperDecoding:
                         with native.CAPTURE_LOCK, torch.cuda.graph(graph, stream=streams[slot], capture_error_mode="thread_local"):
                             sess.decoder_step(gr['tokens'], pos, gr['cross'], gr['kv'], cap, gr['kv'], cap,
                                               gr['logits'], 1, sm, slot=slot, n_past_dev=counter, n_new=1, live_rows=gr['live'],
-                                              not_alone=shared, row_start=gr['row_start'])
+                                              not_alone=shared, row_start=gr['row_start'], cross_group=G, live_groups=gr['live_groups'])
                             token_step(gr, gr['logits'].data_ptr(), V, 0, sm, n_past_dev=counter)
                             finish_step(gr, counter)
                         st['graphs'][gkey], st['counters'][gkey] = graph, counter
@@ -1387,7 +1516,7 @@ class WhisperDecoding:
                             gr['active'] = False
         for s_ in streams:
             main.wait_stream(s_)
-        finish = self._finish_beam_loop if self.beam else self._finish_main_loop
+        finish = self._finish_beam_loop if beam else self._finish_main_loop
         out = finish(st, cur, L0, n_batch, ignore_eot, nsp_dev if self.tokenizer.no_speech is not None else None)
         self._rep_cache = None        # the candidates' repeated features (best_of): the language pass and this loop have both used them
         if one_row and not _retry and self._chain_gave_up("decode loop"):
@@ -1571,16 +1700,18 @@ class WhisperDecoding:
         them and the cross K/V that main_loop left in place into the alignment matrix and its DTW path; timing.words_from_path
         reads the word boundaries off the path.  The pass reuses main_loop's cross K/V (same features: nothing is recomputed)
         and its self-attention cache buffers, so no decode may be in flight.  `num_frames`: mel frames of real audio per
-        utterance (default: the whole window).  Beam search / best_of (n_group > 1) is not supported here in this version
-        (their rows' cross K/V are interleaved per candidate): use torch_word_timestamps.
+        utterance (default: the whole window).  Beam search / best_of (n_group > 1): on a `shared_cross_kv` instance the pass runs
+        over the n_audio winners with group 1, on the one cross K/V set main_loop left in place and the first n_audio rows of its
+        self-attention caches; an instance whose candidates hold a copy each is refused (their rows' cross K/V are interleaved per
+        candidate): use torch_word_timestamps.
         `token_probs`: where the probability of every forced token is computed from the pass's logits -- "torch" (the default:
         an fp32 copy of each call's slab, logsumexp and gather) or "device" (wm_forced_probs, csrc/forced_probs.hip: the fp16
         logits read once; long-form transcription uses it).  The two agree to fp32 rounding, not bit for bit."""
         if token_probs not in ("torch", "device"):
             raise ValueError(f"word_timestamps: token_probs = {token_probs!r}: 'torch' or 'device'")
-        if self.n_group > 1:
+        if self.n_group > 1 and not self.shared_cross_kv:
             raise ValueError("word_timestamps: beam_size / best_of > 1 is not supported on the device path in this version "
-                             "(torch_word_timestamps has no such limit)")
+                             "unless the instance shares its cross K/V (shared_cross_kv=True; torch_word_timestamps has no such limit)")
         if self.use_int8_cross_kv:
             raise native.WmError("word timestamps need fp16 cross-attention K/V; this engine stores int8 codes (WM_FLAG_INT8_CROSS_KV)")
         if self._decode_in_flight:
@@ -1609,13 +1740,13 @@ class WhisperDecoding:
         heads = self.alignment_heads()
         heads_arr = (C.c_int32 * len(heads))(*heads)
         lib, sess, pos = native.load_library(), self.decoder_session, self.positional_embedding
-        st = self._fast_state(n, dev)
+        st = self._fast_state(n * self._cross_group(), dev)      # (shared cross K/V: the candidates' buffer set; n rows of it are used)
         cross = self._cross_persistent(audio_features, st)
         stream = torch.cuda.current_stream().cuda_stream
         tape = torch.empty((n, len(heads), L, 64), dtype=torch.float16, device=dev)
         logits = torch.empty(n * 4 * V, dtype=torch.float16, device=dev)
         probs = torch.zeros((n, L), dtype=torch.float32, device=dev)
-        _, bounds = self._groups(n)
+        _, bounds = self._groups(n, unit=1)
         for g, (lo, hi) in enumerate(bounds):
             kv, cr = [t[lo:hi] for t in st['kv']], [t[lo:hi] for t in cross]
             for off in range(0, L, 4):
@@ -1667,6 +1798,15 @@ class WhisperDecoding:
         return out
 
     # ---- post-processing -------------------------------------------------------------------------------
+    def _call_decoder(self, temperature: Optional[float]):
+        """The decoder of a call at `temperature` (default: the options') and the candidates per utterance it ranks: the instance's
+        own, or -- `fallback_best_of` above temperature 0 -- a sampler over the first fallback_best_of rows (`candidate_mode`)."""
+        t = float(self.options.temperature if temperature is None else temperature)
+        mode, n_cand = candidate_mode(self.options, self.fallback_best_of, t)
+        if self.beam and mode == "sample":
+            return GreedyDecoder(t, self.tokenizer.eot), n_cand
+        return self.decoder, self.n_group
+
     def compression_ratio(self, text) -> float:
         text_bytes = text.encode("utf-8")
         return len(text_bytes) / len(zlib.compress(text_bytes))
@@ -1681,7 +1821,10 @@ class WhisperDecoding:
         assert n_audio == len(no_speech_probs)
         tokens = tokens.reshape(n_audio, self.n_group, -1)
         sum_logprobs = sum_logprobs.reshape(n_audio, self.n_group)
-        tokens, sum_logprobs = self.decoder.finalize(tokens, sum_logprobs)
+        decoder, n_cand = self._call_decoder(temperature)
+        if n_cand < self.n_group:       # a sampling call of a beam instance: the closed rows (sum 0: they would win) never reach the ranker
+            tokens, sum_logprobs = tokens[:, :n_cand], sum_logprobs[:, :n_cand]
+        tokens, sum_logprobs = decoder.finalize(tokens, sum_logprobs)
         eot = self.tokenizer.eot
         tokens = [[t[self.sample_begin: (t == eot).nonzero()[0, 0]] for t in s] for s in tokens]
         selected = self.sequence_ranker.rank(tokens, sum_logprobs)

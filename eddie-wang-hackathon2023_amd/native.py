@@ -86,6 +86,7 @@ EXPORTS = (
     "wm_attn_self_ex", "wm_attn_cross_ex",
     "wm_forced_probs",
     "wm_section_cuts_workspace_bytes", "wm_section_cuts",
+    "wm_step_finish_group", "wm_attn_cross_group_ex", "wm_decoder_step_group",
 )
 
 
@@ -146,6 +147,11 @@ class WmDecoderIO(C.Structure):
         ("not_alone", C.c_int32),
         ("row_start", C.c_void_p),
     ]
+
+
+class WmDecoderGroupIO(C.Structure):
+    """wm_decoder_group_io (include/whisper_mi355.h): a decoder call whose rows share cross K/V in groups of `cross_group`."""
+    _fields_ = [("io", WmDecoderIO), ("cross_group", C.c_int32), ("live_groups", C.c_void_p)]
 
 
 class WmGemvIO(C.Structure):
@@ -270,6 +276,11 @@ class WmAttnCrossIO(C.Structure):
     ]
 
 
+class WmAttnCrossGroupIO(C.Structure):
+    """wm_attn_cross_group_io (include/whisper_mi355.h): wm_attn_cross_io for candidate groups that share one K/V row (tests)."""
+    _fields_ = WmAttnCrossIO._fields_ + [("G", C.c_int32), ("live_utt", C.c_void_p)]
+
+
 class WmTapIO(C.Structure):
     """wm_tap_io (include/whisper_mi355.h): where wm_decoder_step_tap writes the cross-attention queries."""
     _fields_ = [("q_tape", C.c_void_p), ("capacity", C.c_int32), ("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32)]
@@ -334,6 +345,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_decoder_workspace_bytes.argtypes = [vp, i32, i32]
     lib.wm_decoder_workspace_bytes.restype = sz
     lib.wm_decoder_step.argtypes = [vp, C.POINTER(WmDecoderIO), vp]
+    lib.wm_decoder_step_group.argtypes = [vp, C.POINTER(WmDecoderGroupIO), vp]
     lib.wm_greedy_step.argtypes = [C.POINTER(WmGreedyIO), vp]
     lib.wm_gemm.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, sz, vp]
     lib.wm_conv1d_gelu.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp]
@@ -378,6 +390,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_row_finish.argtypes = [C.POINTER(WmRowFinishIO), vp]
     lib.wm_attn_self_ex.argtypes = [C.POINTER(WmAttnSelfIO), vp]
     lib.wm_attn_cross_ex.argtypes = [C.POINTER(WmAttnCrossIO), vp]
+    lib.wm_attn_cross_group_ex.argtypes = [C.POINTER(WmAttnCrossGroupIO), vp]
+    lib.wm_step_finish_group.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.wm_embed.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp]
     lib.wm_mel_transpose_pad.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.wm_zero_pad_rows.argtypes = [vp, i32, i32, i32, vp]

@@ -33,8 +33,10 @@ def parse_arguments(argv=None):
     parser.add_argument('--vocab', type=str, default=None, help='path to multilingual.tiktoken (text output)')
     parser.add_argument('--beam_size', type=int, default=None, help='beam search with that many beams (1..8; default: greedy)')
     parser.add_argument('--patience', type=float, default=None, help='beam search: finished candidates per utterance = beam_size * patience')
+    parser.add_argument('--shared_cross_kv', default=False, action='store_true',
+                        help="beam search: the beams of an utterance read one copy of its cross-attention K/V (off by default); lets --word_timestamps run with --beam_size")
     parser.add_argument('--word_timestamps', default=False, action='store_true',
-                        help='print "start-end word (probability)" lines after the text (cross-attention alignment + DTW on the device; greedy decoding only)')
+                        help='print "start-end word (probability)" lines after the text (cross-attention alignment + DTW on the device; with --beam_size it needs --shared_cross_kv)')
     return parser.parse_args(argv)
 
 
@@ -64,13 +66,15 @@ def real_mel_frames(input_file: str):
 
 
 def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', input_file: str = 'synthetic',
-             vocab: str = None, beam_size: int = None, patience: float = None, word_timestamps: bool = False):
+             vocab: str = None, beam_size: int = None, patience: float = None, word_timestamps: bool = False,
+             shared_cross_kv: bool = False):
     logging.basicConfig(level=getattr(logging, log_level.upper(), logging.ERROR))
     torch.cuda.set_device(0)
     mel = load_mel(input_file).to('cuda').type(torch.float16).unsqueeze(0)
     engine_dir = Path(engine_dir)
     whisper_encoding = WhisperEncoding(engine_dir)
-    whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=DecodingOptions(beam_size=beam_size, patience=patience))
+    whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=DecodingOptions(beam_size=beam_size, patience=patience),
+                                       shared_cross_kv=shared_cross_kv)
     begin_time = time.time()
     audio_features = whisper_encoding.get_audio_features(mel)
     languages, language_probs = whisper_decoding.detect_language(audio_features)

@@ -214,10 +214,13 @@ class Session(object):
                         n_past: int, qkv_amax: Optional[torch.Tensor] = None, slot: int = 0,
                         n_past_dev: Optional[torch.Tensor] = None, n_new: Optional[int] = None,
                         live_rows: Optional[torch.Tensor] = None, not_alone: bool = False,
-                        row_start: Optional[torch.Tensor] = None) -> WmDecoderIO:
+                        row_start: Optional[torch.Tensor] = None, cross_group: int = 1,
+                        live_groups: Optional[torch.Tensor] = None) -> WmDecoderIO:
         """The wm_decoder_io of one call.  tokens int32 [B, L] (any row stride: a column window of a wider
         buffer works); past/present per layer [B,2,H,capacity,64]; present may be the same tensors as past
-        (in-place append).  The struct keeps its pointer arrays alive (`io._keep`)."""
+        (in-place append).  `cross_group` = G > 1: rows a * G .. a * G + G - 1 share row a of `cross` [B / G, ...] (candidate groups,
+        whisper_mi355.h: the io of a wm_decoder_group_io, `make_decoder_group_io`); with `live_rows` it needs `live_groups` (int32
+        [1 + B / G], wm_step_finish_group).  The struct keeps its pointer arrays alive (`io._keep`)."""
         lib = self._engine.lib
         b, l = tokens.shape
         if n_new is not None:          # device step counter: `tokens` is the whole [B, capacity] buffer
@@ -225,8 +228,12 @@ class Session(object):
         assert tokens.dtype == torch.int32 and tokens.stride(1) == 1
         for name, group in (("cross", cross), ("present", present), ("past", past or ())):
             for t in group:
-                if t.shape[0] != b:     # raw pointers cross the C ABI: a short buffer would be read out of bounds
-                    raise native.WmError(f"decoder step: {name} K/V holds {t.shape[0]} utterances, tokens hold {b}")
+                want = b // cross_group if name == "cross" and cross_group > 1 else b
+                if t.shape[0] != want:     # raw pointers cross the C ABI: a short buffer would be read out of bounds
+                    raise native.WmError(f"decoder step: {name} K/V holds {t.shape[0]} utterances, tokens hold {b}"
+                                         + (f" in groups of {cross_group}" if name == "cross" and cross_group > 1 else ""))
+        if cross_group > 1 and b % cross_group:
+            raise native.WmError(f"decoder step: {b} rows are not a multiple of cross_group = {cross_group}")
         if logits.shape[0] != b:
             raise native.WmError(f"decoder step: logits hold {logits.shape[0]} utterances, tokens hold {b}")
         ws = self._workspace(("dec", b, l, slot), lib.wm_decoder_workspace_bytes(self._engine.handle, b, l))
@@ -255,12 +262,30 @@ class Session(object):
         if row_start is not None:      # int32 [B]: the slot each row's sequence begins at (right-aligned rows, whisper_mi355.h)
             assert row_start.dtype == torch.int32 and row_start.numel() == b and row_start.is_contiguous()
         io.row_start = row_start.data_ptr() if row_start is not None else None
-        io._keep = (past_arr, present_arr, cross_arr, ws, live_rows, row_start)
+        if live_groups is not None:    # int32 [1 + B / G]: count, then the utterances that still have a live row
+            assert live_groups.dtype == torch.int32 and live_groups.numel() >= 1 + b // max(1, cross_group) and live_groups.is_contiguous()
+        io._keep = (past_arr, present_arr, cross_arr, ws, live_rows, row_start, live_groups)
         return io
+
+    def make_decoder_group_io(self, *args, cross_group: int = 1, live_groups: Optional[torch.Tensor] = None, **kw):
+        """The wm_decoder_group_io of one call: `make_decoder_io(...)` with its group size and the list of live utterances."""
+        io = self.make_decoder_io(*args, cross_group=cross_group, live_groups=live_groups, **kw)
+        gio = native.WmDecoderGroupIO()
+        gio.io = io                    # (a copy of the struct: the pointer arrays it names stay alive through `_keep`)
+        gio.cross_group = int(cross_group) if cross_group > 1 else 0
+        gio.live_groups = live_groups.data_ptr() if live_groups is not None and cross_group > 1 else None
+        gio._keep = io
+        return gio
 
     def decoder_step(self, tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
                      stream: int, qkv_amax=None, slot: int = 0, n_past_dev=None, n_new=None, live_rows=None, not_alone: bool = False,
-                     row_start=None):
+                     row_start=None, cross_group: int = 1, live_groups=None):
+        if cross_group > 1:            # candidates that share their utterance's cross K/V
+            gio = self.make_decoder_group_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
+                                             qkv_amax, slot, n_past_dev, n_new, live_rows, not_alone, row_start,
+                                             cross_group=cross_group, live_groups=live_groups)
+            check(self._engine.lib.wm_decoder_step_group(self._engine.handle, C.byref(gio), stream), "wm_decoder_step_group")
+            return
         io = self.make_decoder_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
                                   qkv_amax, slot, n_past_dev, n_new, live_rows, not_alone, row_start)
         check(self._engine.lib.wm_decoder_step(self._engine.handle, C.byref(io), stream), "wm_decoder_step")

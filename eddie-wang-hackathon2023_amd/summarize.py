@@ -296,7 +296,8 @@ def main(args) -> Optional[dict]:
     engine_dir = Path(args.engine_dir)
     only_torch = not args.test_trt_llm                 # the PyTorch path alone needs the engine directory's configuration, not its engines
     whisper_encoding = WhisperEncoding(engine_dir, only_torch=only_torch)
-    whisper_decoding = WhisperDecoding(engine_dir, only_torch=only_torch, vocab_path=args.vocab, options=decoding_options(args))
+    whisper_decoding = WhisperDecoding(engine_dir, only_torch=only_torch, vocab_path=args.vocab, options=decoding_options(args),
+                                       shared_cross_kv=bool(getattr(args, 'shared_cross_kv', False)) and not only_torch)
     if args.sample_len:
         whisper_decoding.sample_len = args.sample_len
     pairs = discover(args.dataset_dir)
@@ -345,6 +346,8 @@ def parse_arguments(argv=None):
                         help='run the encoder of the next batch beside the decode loop of the current one (eval_engines_stream)')
     parser.add_argument('--beam_size', type=int, default=None, help='beam search with that many beams (1..8; default: greedy)')
     parser.add_argument('--patience', type=float, default=None, help='beam search: finished candidates per utterance = beam_size * patience')
+    parser.add_argument('--shared_cross_kv', default=False, action='store_true',
+                        help="beam search: the beams of an utterance read one copy of its cross-attention K/V (off by default)")
     return parser.parse_args(argv)
 
 

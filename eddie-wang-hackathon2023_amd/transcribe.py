@@ -35,13 +35,16 @@ longform.py states the contract (the rules and the schedule, on the host, tested
 
 Refused (ValueError): an instance built with `prompt` / `prefix` (use `initial_prompt`), conditioning or an initial prompt on
 an instance without `row_prompts`, beam_size / best_of together with a ladder of more than one temperature, and word timestamps
-with beam_size / best_of; word timestamps on an engine with int8 cross K/V raise WhisperDecoding.word_timestamps' own error.  Out of
+with beam_size / best_of -- unless the instance shares its cross K/V (WhisperDecoding(shared_cross_kv=True): word timestamps for
+candidates) and names its sampling mode (beam_size with fallback_best_of: beam search at temperature 0, samples above -- upstream's
+`whisper audio.wav` recipe with the full ladder, conditioning and sections; best_of alone keeps the one-temperature rule); word
+timestamps on an engine with int8 cross K/V raise WhisperDecoding.word_timestamps' own error.  Out of
 scope: clip_timestamps, the hallucination-silence heuristics (hallucination_silence_threshold).  Files at any rate from 4 kHz to 192 kHz and with
 several channels are downmixed and resampled to 16 kHz on the device (whisper_utils.load_audio_device, wm_resample).
 
 CLI: python transcribe.py --engine_dir eng --input_file a.flac [b.flac ...] --vocab multilingual.tiktoken [--temperature T ...]
 [--no_fallback] [--condition_on_previous_text] [--initial_prompt TEXT] [--word_timestamps] [--sections [--section_seconds S]
-[--min_section_seconds S]] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
+[--min_section_seconds S]] [--beam_size K [--patience P]] [--best_of M] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
 line per non-empty segment, and with --word_timestamps one "start-end word (probability)" line per word under it.
 """
 from __future__ import annotations
@@ -70,9 +73,9 @@ def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], co
     """The combinations this version refuses (module docstring)."""
     opt = decoding.options
     if word_timestamps:
-        if decoding.beam or decoding.n_group != 1:
+        if (decoding.beam or decoding.n_group != 1) and not getattr(decoding, 'shared_cross_kv', False):
             raise ValueError("transcribe: word_timestamps with beam_size / best_of is not supported in this version (the device "
-                             "alignment reads one row of cross K/V per file)")
+                             "alignment reads one row of cross K/V per file) unless the instance was built with shared_cross_kv=True")
         if getattr(decoding, 'use_int8_cross_kv', False):
             raise native.WmError("word timestamps need fp16 cross-attention K/V; this engine stores int8 codes (WM_FLAG_INT8_CROSS_KV)")
     if opt.prompt or opt.prefix:
@@ -81,7 +84,7 @@ def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], co
     if (condition_on_previous_text or initial_prompt) and not getattr(decoding, 'row_prompts', False):
         raise ValueError("transcribe: condition_on_previous_text / initial_prompt need a WhisperDecoding built with row_prompts=True "
                          "(every row carries its own prompt; the start length is fixed at construction)")
-    if decoding.beam or decoding.n_group != 1:
+    if (decoding.beam or decoding.n_group != 1) and getattr(decoding, 'fallback_best_of', None) is None:
         if len(temperatures) != 1 or float(temperatures[0]) != float(opt.temperature):
             raise ValueError("transcribe: beam_size / best_of decode at the instance's temperature: give that one temperature "
                              f"({opt.temperature}; no fallback), not the ladder {tuple(temperatures)}")
@@ -318,7 +321,8 @@ def _transcribe_files(encoding: WhisperEncoding, decoding: WhisperDecoding, mels
         if getattr(decoding, 'row_prompts', False):
             decoding.set_prompts(prompts)                # (None without conditioning / an initial prompt: every row starts bare)
         limit = torch.tensor([(1 << 30) if on else 0 for on in live], dtype=torch.int32).repeat_interleave(n_group)
-        per_call = None if (decoding.beam or n_group != 1) else temperature
+        # (candidates decode at the instance's temperature -- but for beam search with fallback_best_of, whose calls name theirs)
+        per_call = None if ((decoding.beam or n_group != 1) and getattr(decoding, 'fallback_best_of', None) is None) else temperature
         tokens, sum_logprobs, no_speech_probs = decoding.main_loop(features, row_limit=limit, temperature=per_call)
         results = decoding.post_process(tokens, sum_logprobs, no_speech_probs, features, state['languages'], temperature=temperature)
         results = [r if on else None for r, on in zip(results, live)]
@@ -392,13 +396,35 @@ def parse_arguments(argv=None):
                         help="decode every window with the file's text so far as its prompt (upstream's default; off here)")
     parser.add_argument('--initial_prompt', type=str, default=None, help="text in front of every file's first window: names, spelling, style")
     parser.add_argument('--word_timestamps', default=False, action='store_true',
-                        help='print "start-end word (probability)" lines under every segment (cross-attention alignment + DTW on the device; greedy decoding only)')
+                        help='print "start-end word (probability)" lines under every segment (cross-attention alignment + DTW on the device)')
     parser.add_argument('--sections', default=False, action='store_true',
                         help='cut every file where it is quietest and decode the sections side by side: one long file fills the batch '
                              '(no text or timestamp crosses a cut; conditioning keeps its history per section)')
     parser.add_argument('--section_seconds', type=float, default=SectionOptions.max_seconds, help='longest section (default: 30)')
     parser.add_argument('--min_section_seconds', type=float, default=None, help='shortest section but for the last (default: half the longest)')
+    parser.add_argument('--beam_size', type=int, default=None,
+                        help='beam search at temperature 0 with this many beams (default: greedy); the beams share one copy of the cross K/V, '
+                             'and above temperature 0 the ladder draws --best_of samples per window (default 1), at most beam_size')
+    parser.add_argument('--patience', type=float, default=None, help='beam search patience (needs --beam_size)')
+    parser.add_argument('--best_of', type=int, default=None,
+                        help='samples per window above temperature 0.  Without --beam_size every window is decoded as best_of samples at '
+                             'ONE temperature: give exactly one --temperature above 0 (a per-call temperature, i.e. the ladder, is refused)')
     return parser.parse_args(argv)
+
+
+def build_decoding(args, engine_dir, prompted: bool) -> WhisperDecoding:
+    """The WhisperDecoding of the command line: greedy as ever; --beam_size: beam search at 0 and --best_of samples above on one
+    shared copy of the cross K/V; --best_of alone: best_of samples at the one temperature given."""
+    if args.beam_size is not None:
+        options = DecodingOptions(language=args.language, beam_size=args.beam_size, patience=args.patience)
+        return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,
+                               fallback_best_of=args.best_of if args.best_of is not None else 1)
+    if args.patience is not None:
+        raise ValueError("--patience needs --beam_size")
+    if args.best_of is not None:
+        options = DecodingOptions(language=args.language, best_of=args.best_of, temperature=float(args.temperature[0]))
+        return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True)
+    return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language), row_prompts=prompted)
 
 
 def main(args) -> List[dict]:
@@ -407,7 +433,7 @@ def main(args) -> List[dict]:
     engine_dir = Path(args.engine_dir)
     encoding = WhisperEncoding(engine_dir)
     prompted = bool(args.condition_on_previous_text or args.initial_prompt)
-    decoding = WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language), row_prompts=prompted)
+    decoding = build_decoding(args, engine_dir, prompted)
     temperatures = tuple(args.temperature[:1] if args.no_fallback else args.temperature)
     results = transcribe(encoding, decoding, args.input_file, temperatures=temperatures, n_rows=args.rows,
                          condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt,

@@ -63,6 +63,8 @@ typedef struct wm_dims {
  *   8  (round 6) wm_decoder_io gains `not_alone` (appended): the caller says when other decoder steps may run beside this one
  *      (still 8, like wm_mel_windows / wm_resample) wm_decoder_io gains `row_start` (appended; NULL = as before); wm_attn_decode_self_rows
  *      (still 8: test-only entries, no existing struct or signature changed) wm_attn_self_ex, wm_attn_cross_ex
+ *      (still 8: entries and structs of their own, no existing struct or signature changed) wm_decoder_step_group / wm_decoder_group_io,
+ *      wm_step_finish_group, wm_attn_cross_group_ex
  *      (still 8: an entry only) wm_forced_probs
  *      (still 8: entries only) wm_section_cuts, wm_section_cuts_workspace_bytes */
 #define WM_ABI_VERSION 8
@@ -185,6 +187,32 @@ typedef struct wm_decoder_io {
 size_t wm_decoder_workspace_bytes(const wm_engine* e, int batch, int n_new);
 int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t stream);
 
+/* ---- candidate groups: one copy of the cross-attention K/V per utterance (added within ABI 8: a struct and entries of their own; wm_decoder_io
+ * keeps its layout) ----
+ * wm_decoder_step for rows that come in groups of G = cross_group consecutive rows -- the beams or best_of samples of utterance a are rows
+ * a * G .. a * G + G - 1 -- which share ONE copy of the utterance's cross-attention K/V.  cross_group 0 or 1: exactly wm_decoder_step(io).
+ * With G > 1, `io.cross[i]` is [batch / G, 2, n_head, n_audio_ctx, 64]; batch % G == 0 and G * min(n_new, 4) <= 8 (a call of more than 4
+ * tokens runs as 4-token passes, so it takes G = 2 at most; the candidates of an utterance begin with the same tokens, so a caller prefills
+ * ONE row per utterance with wm_decoder_step on the same buffers and copies its cache rows and logits to the candidates -- WhisperDecoding
+ * does).  Everything else (tokens, caches, logits, live_rows) stays per row.
+ *   - n_new == 1: one item of the cross-attention launch streams K/V row a once and serves the utterance's G rows; a row's context has the
+ *     bits it has in wm_decoder_step on K/V repeated G times at the same number of key-range pieces.  The pieces are chosen for the items
+ *     the launch has (n_head * batch / G * pieces), so that number may differ from the repeated call's: across it the logits agree within
+ *     the decoder's usual bound, not bit for bit.
+ *   - n_new > 1 (prefill passes): a row's own item reads K/V row b / G.
+ *   - with io.live_rows, `live_groups` must be given: device int32 [1 + batch / G], word 0 = the number of utterances that still have a
+ *     live row, then their indices, ascending (wm_step_finish_group maintains both lists).  An utterance that is not listed is not read; a
+ *     finished row of a listed utterance gets finite, unspecified logits, as ever.  Read only when n_new == 1.
+ *   - such a call never takes a one-launch form (as if io.not_alone were set); wm_decoder_workspace_bytes(batch, n_new) covers it.
+ * wm_decoder_step_multi and wm_decoder_step_tap take a wm_decoder_io and so know no groups: the CU-partitioned schedule and the forced pass of
+ * the word timestamps run one row per utterance.                                                                                      */
+typedef struct wm_decoder_group_io {
+    wm_decoder_io io;
+    int32_t cross_group;
+    const int32_t* live_groups;
+} wm_decoder_group_io;
+int wm_decoder_step_group(const wm_engine* e, const wm_decoder_group_io* gio, wm_stream_t stream);
+
 /* The same step for n_groups (<= 8) independent utterance groups at once, scheduled for the chip:
  * group g's latency-bound kernels (weight-streaming GEMMs, row kernels, self-attention) are enqueued on
  * light_streams[g]; every group's cross-attention kernel -- the HBM-bound part, 245.76 MB per utterance --
@@ -236,6 +264,10 @@ int wm_step_advance(int32_t* counter, wm_stream_t stream);
  * is rebuilt from the flags: live[0] = number of rows with done[b] == 0, live[1..] = their indices, ascending.
  * batch <= 1024. */
 int wm_step_finish(int32_t* counter, const int32_t* done, int batch, int32_t* live, wm_stream_t stream);
+/* The same for candidate groups of `group` consecutive rows (batch % group == 0; wm_decoder_group_io::cross_group), and next to `live` the
+ * list of the utterances that still have a live row: live_groups[0] = their number, live_groups[1..] = their indices, ascending
+ * (int32 [1 + batch / group]).  Added under ABI 8 (an entry only). */
+int wm_step_finish_group(int32_t* counter, const int32_t* done, int batch, int group, int32_t* live, int32_t* live_groups, wm_stream_t stream);
 
 /* ---- beam search step (added within ABI 8: new entries only, no existing struct or signature changed) ----------------
  * The semantics of upstream Whisper's BeamSearchDecoder.update on the device, one call per token step of an utterance
@@ -448,6 +480,29 @@ typedef struct wm_attn_cross_io {
     int32_t skip_zero_rows;
 } wm_attn_cross_io;
 int wm_attn_cross_ex(const wm_attn_cross_io* io, wm_stream_t stream);
+/* wm_attn_cross_ex for candidate groups (AttnCrossParams::G; wm_decoder_group_io::cross_group): rows a * G .. a * G + G - 1 read K/V row a of
+ * kv [B / G][2][H][Tk][64].  L == 1: one item per (head, utterance, key-range piece) serves the G queries of the utterance from one K/V
+ * stream; with the same nsplit, ksplit and skip setting every live row has the bits wm_attn_cross_ex gives for B rows on K/V repeated
+ * G times.  L > 1: the row's own item reads K/V row b / G.  ws stays indexed by the ORIGINAL row.  live_utt (DEVICE int32
+ * [1 + B / G], L == 1 with `live` only): count, then the utterances to read -- an utterance that is not listed is not read and none of
+ * its rows' outputs or workspace blocks are touched; a row of a listed utterance that is not on `live` gets finite, unspecified output.
+ * Refused (rc 1, nothing launched): G < 1, B % G != 0, G * L > 8, live without live_utt (G > 1, L == 1) or live_utt without it, and
+ * everything wm_attn_cross_ex refuses.  Added under ABI 8 (an entry and a struct of its own). */
+typedef struct wm_attn_cross_group_io {
+    const float* part; int32_t ksplit, ldp; int64_t part_sstride;
+    const void* bias;
+    int32_t B, L, H, Tk;
+    const void* kv; int64_t kv_bstride;
+    float kv_q8_scale;
+    void* out; int32_t ldo;
+    int32_t nsplit;
+    float* ws;
+    const int32_t* live;
+    int32_t skip_zero_rows;
+    int32_t G;
+    const int32_t* live_utt;
+} wm_attn_cross_group_io;
+int wm_attn_cross_group_ex(const wm_attn_cross_group_io* io, wm_stream_t stream);
 /* x[r] = fp16(E[token of row r] + pos[r % L + T]), r < M = B * L; token of row r = tokens[(r / L) * tokens_ld + r % L + T];
  * T = *t_dev when given, else 0.  emb_tiles: the fp16 embedding in tile-linear layout (weight.py: tile_linear), C a multiple
  * of 32; token ids are clamped to [0, n_vocab).  generation (optional): incremented once per call. */
