@@ -572,6 +572,7 @@ int prof_slot(Profiler& pr, int layer, hipStream_t s) {
 }
 
 struct DecWs { h16 *x, *xn, *ctx, *hid; float* part; float* cross_ws; size_t part_elems; int nsplit; size_t total;
+               h16* logit_stage;                // block prefill only: logits rows of a chunk of utterances before they are scattered
                unsigned long long *gran_x, *gran_h, *gran_q, *gran_c, *gran_p, *gran_s; wm::ChainLayerIo* layer_io; unsigned* generation; };      // granule edges of the one-row chain (gemv_chain.hip) and its call counter
 
 int cross_nsplit(int B, int H) {
@@ -603,7 +604,9 @@ int cross_nsplit_most(int B, int H, int L) {
     return n;
 }
 
-DecWs carve_decoder(const wm_engine* e, int B, int L, void* ws, int G = 1) {
+// lean (wm_decoder_prefill): no key-range pieces and no one-launch state -- the block prefill never takes those forms -- and a staging
+// block of at most SKINNY_MAX_M logits rows instead; everything else is the decode step's layout at M = B * L rows, linear in M
+DecWs carve_decoder(const wm_engine* e, int B, int L, void* ws, int G = 1, bool lean = false) {
     const wm_dims& d = e->dims;
     const size_t C = d.n_text_state, M = (size_t)B * L;
     Carver c{(unsigned char*)ws, 0};
@@ -622,6 +625,14 @@ DecWs carve_decoder(const wm_engine* e, int B, int L, void* ws, int G = 1) {
     w.part_elems = widest * M;
     w.part = c.take<float>(w.part_elems);
     w.nsplit = cross_nsplit_group(B, d.n_text_head, L, G);
+    w.logit_stage = nullptr;
+    if (lean) {
+        w.cross_ws = nullptr;
+        w.gran_x = w.gran_h = w.gran_q = w.gran_c = w.gran_p = w.gran_s = nullptr; w.layer_io = nullptr; w.generation = nullptr;
+        w.logit_stage = c.take<h16>((M < (size_t)SKINNY_MAX_M ? M : (size_t)SKINNY_MAX_M) * d.n_vocab);
+        w.total = align_up(c.off);
+        return w;
+    }
     w.cross_ws = c.take<float>((size_t)B * d.n_text_head * cross_nsplit_most(B, d.n_text_head, L) * L * 66);
     const size_t R = M < (size_t)CHAIN_MAX_ROWS ? M : (size_t)CHAIN_MAX_ROWS;      // rows the one-launch step serves (gemv_chain.hip): every edge [rows][...]
     w.gran_x = c.take<unsigned long long>(R * (C / 2) + 8);
@@ -788,6 +799,7 @@ struct GroupStep {
     int chain_wgs = 0; unsigned* chain_err = nullptr; ChainDev* chain_cd = nullptr;
     bool rows = false;                           // the fused row-split path (gemm_rows.hip)
     bool fused() const { return small || rows; }
+    bool prefill = false; int logits_from = 0;   // wm_decoder_prefill: any L on an empty cache, attn_prefill.hip's kernels, logits from a position on
 
     // one Linear of the small-batch path.  mode as epilogue.h; ln_g != null: LayerNorm of the input rows (the residual stream)
     // inside the kernel
@@ -818,23 +830,24 @@ struct GroupStep {
     int init(const wm_engine* e_, const wm_decoder_io* io_, hipStream_t stream, bool alone = true, int cross_group = 0,
              const int32_t* live_groups_ = nullptr) {
         e = e_; io = io_; live_groups = live_groups_;
+        const char* who = prefill ? "wm_decoder_prefill" : "wm_decoder_step";      // the entry a refusal names
         prof = &g_prof_dev[e->device >= 0 && e->device < MAX_DEVICES ? e->device : 0];
         WM_REQUIRE(io && io->tokens && io->positional_embedding && io->present && io->cross && io->logits && io->workspace,
-                   "wm_decoder_step: null argument");
+                   "%s: null argument", who);
         const wm_dims& d = e->dims;
         B = io->batch; L = io->n_new; T = io->n_past; C = d.n_text_state; H = d.n_text_head; M = B * L;
-        WM_REQUIRE(B >= 1 && L >= 1 && L <= 4 && T >= 0, "wm_decoder_step: bad batch/n_new/n_past (%d, %d, %d)", B, L, T);
-        WM_REQUIRE(T + L <= d.n_text_ctx, "wm_decoder_step: T+L=%d exceeds n_text_ctx=%d", T + L, d.n_text_ctx);
-        WM_REQUIRE(T == 0 || io->past, "wm_decoder_step: n_past > 0 needs past buffers");
-        WM_REQUIRE(T == 0 || io->past_capacity >= T, "wm_decoder_step: past capacity %d < n_past %d", io->past_capacity, T);
-        WM_REQUIRE(io->present_capacity >= T + L, "wm_decoder_step: present capacity %d < n_past + n_new = %d", io->present_capacity, T + L);
-        WM_REQUIRE(!io->n_past_dev || (L == 1 && io->past), "wm_decoder_step: a device step counter needs n_new == 1 and past buffers");
+        WM_REQUIRE(B >= 1 && L >= 1 && (prefill || L <= 4) && T >= 0, "%s: bad batch/n_new/n_past (%d, %d, %d)", who, B, L, T);
+        WM_REQUIRE(T + L <= d.n_text_ctx, "%s: T+L=%d exceeds n_text_ctx=%d", who, T + L, d.n_text_ctx);
+        WM_REQUIRE(T == 0 || io->past, "%s: n_past > 0 needs past buffers", who);
+        WM_REQUIRE(T == 0 || io->past_capacity >= T, "%s: past capacity %d < n_past %d", who, io->past_capacity, T);
+        WM_REQUIRE(io->present_capacity >= T + L, "%s: present capacity %d < n_past + n_new = %d", who, io->present_capacity, T + L);
+        WM_REQUIRE(!io->n_past_dev || (L == 1 && io->past), "%s: a device step counter needs n_new == 1 and past buffers", who);
         WM_REQUIRE(C == H * 64, "head size must be 64");
         G = cross_group > 1 ? cross_group : 1;
-        WM_REQUIRE(cross_group >= 0 && B % G == 0 && G * L <= CROSS_GROUP_MAX,
+        WM_REQUIRE(cross_group >= 0 && B % G == 0 && (prefill || G * L <= CROSS_GROUP_MAX),
                    "wm_decoder_step_group: cross_group=%d needs batch=%d a multiple of it and cross_group * n_new=%d <= %d", cross_group, B, G * L, CROSS_GROUP_MAX);
         WM_REQUIRE(!(G > 1 && L == 1 && io->live_rows) || live_groups, "wm_decoder_step_group: cross_group with live_rows needs live_groups (wm_step_finish_group)");
-        w = carve_decoder(e, B, L, io->workspace, G);
+        w = carve_decoder(e, B, L, io->workspace, G, prefill);
         WM_REQUIRE(io->workspace_bytes >= w.total, "decoder workspace too small: %zu < %zu", io->workspace_bytes, w.total);
         small = M <= small_path_max_rows();
         rows = !small && rows_path_min_rows() > 0 && M >= rows_path_min_rows() && !e->dec.empty() && gemm_rows_supports(C, e->dec[0].qkv.wcode);
@@ -846,9 +859,9 @@ struct GroupStep {
         // step -- and of everything decoded from it -- are invalid.  Every decoder call fails loudly until the caller has looked.
         // (Not while a stream is being captured: the call issues no work then, and failing it would abort the caller's capture.)
         if (!capturing && chain_err_peek(cd) != 0) {
-            set_error("wm_decoder_step: a one-launch decode step on device %d gave up waiting for its workgroups (they were not resident "
+            set_error("%s: a one-launch decode step on device %d gave up waiting for its workgroups (they were not resident "
                       "together): the results since then are invalid.  Call wm_decode_chain_error() to acknowledge and decode again -- the device "
-                      "takes the launch-per-kernel path from then on (wm_set_decode_chain re-arms the one-launch forms)", e->device);
+                      "takes the launch-per-kernel path from then on (wm_set_decode_chain re-arms the one-launch forms)", who, e->device);
             return 1;
         }
         if (alone && small && L == 1 && M <= chain_max_rows() && !e->dec.empty() && e->chain_dev && g_decode_chain.load(std::memory_order_relaxed) && !io->qkv_amax) {
@@ -1052,7 +1065,7 @@ struct GroupStep {
             mark(i, 12, s);
             return 0;
         }
-        if (launch_attn_self(p, s)) return 2;
+        if (prefill ? launch_attn_prefill_self(p, s) : launch_attn_self(p, s)) return 2;
         mark(i, 2, s);
         if (fused()) {
             if (gemv(Lr.out, w.ctx, C, 2, nullptr, nullptr, nullptr, 0, s)) return 2;    // x += out(ctx)
@@ -1094,6 +1107,7 @@ struct GroupStep {
         p.kv_q8_scale = e->i8cross() ? Lr.cross_scale : 0.f;
         p.out = w.ctx; p.ldo = C; p.nsplit = w.nsplit; p.ws = w.cross_ws;
         p.live = io->live_rows;
+        if (prefill) return launch_attn_prefill_cross(p, s) ? 2 : 0;
         p.G = G; p.live_utt = (G > 1 && L == 1 && io->live_rows) ? live_groups : nullptr;
         p.skip_zero_rows = g_cross_v_skip.load(std::memory_order_relaxed);
         const int slot = (L == 1) ? prof_slot(*prof, i, s) : -1;
@@ -1120,7 +1134,8 @@ struct GroupStep {
             if (skinny_all(Lr.mlp2, w.hid, 4 * C, M, w.part, &ks, s)) return 2;
             mark(i, 11, s);
             const bool last_ = (i + 1 == d.n_text_layer);
-            const int rc = finish(Lr.mlp2, ks, 0, last_ ? e->lnfg : e->dec[i + 1].ln1g, last_ ? e->lnfb : e->dec[i + 1].ln1b, w.xn, C, C, s);
+            const int rc = (prefill && last_) ? finish(Lr.mlp2, ks, 3, nullptr, nullptr, nullptr, 0, C, s)      // (the final LayerNorm: end_prefill, on the rows it keeps)
+                                              : finish(Lr.mlp2, ks, 0, last_ ? e->lnfg : e->dec[i + 1].ln1g, last_ ? e->lnfb : e->dec[i + 1].ln1b, w.xn, C, C, s);
             mark(i, 12, s);
             return rc;
         }
@@ -1135,7 +1150,8 @@ struct GroupStep {
         if (skinny_all(Lr.mlp2, w.hid, 4 * C, M, w.part, &ks, s)) return 2;
         mark(i, 11, s);
         const bool last = (i + 1 == d.n_text_layer);
-        const int rc = finish(Lr.mlp2, ks, 0, last ? e->lnfg : e->dec[i + 1].ln1g, last ? e->lnfb : e->dec[i + 1].ln1b, w.xn, C, C, s);
+        const int rc = (prefill && last) ? finish(Lr.mlp2, ks, 3, nullptr, nullptr, nullptr, 0, C, s)
+                                         : finish(Lr.mlp2, ks, 0, last ? e->lnfg : e->dec[i + 1].ln1g, last ? e->lnfb : e->dec[i + 1].ln1b, w.xn, C, C, s);
         mark(i, 12, s);
         return rc;
     }
@@ -1157,6 +1173,50 @@ struct GroupStep {
             p.Wt = e->emb_t; p.n_blocks = e->emb_blocks; p.w8 = 0; p.ksplit = 1;
             p.out = (h16*)io->logits + (size_t)r0 * d.n_vocab; p.ldc = d.n_vocab; p.n_valid = d.n_vocab;
             if (launch_gemm_skinny(p, s)) return 2;
+        }
+        return 0;
+    }
+
+    // final LayerNorm + logits of `R` consecutive rows of `src` (row stride C) -> `dst` (row stride n_vocab); w.xn holds the normalised rows
+    int logits_rows(const h16* src, int R, h16* dst, hipStream_t s) {
+        const wm_dims& d = e->dims;
+        if (launch_layernorm(src, C, R, C, e->lnfg, e->lnfb, w.xn, C, s)) return 2;
+        if (R <= small_path_max_rows()) {
+            GemvSmallParams p{};
+            p.A = w.xn; p.lda = C; p.M = R; p.K = C; p.Wt = e->emb_t; p.n_blocks = e->emb_blocks; p.w8 = 0;
+            p.mode = 3; p.out16 = dst; p.ld16 = d.n_vocab; p.n_valid = d.n_vocab;
+            return launch_gemv_small(p, s);
+        }
+        for (int r0 = 0; r0 < R; r0 += SKINNY_MAX_M) {
+            GemmSkinnyParams p{};
+            p.A = w.xn + (size_t)r0 * C; p.lda = C; p.M = (R - r0) < SKINNY_MAX_M ? (R - r0) : SKINNY_MAX_M; p.K = C;
+            p.Wt = e->emb_t; p.n_blocks = e->emb_blocks; p.w8 = 0; p.ksplit = 1;
+            p.out = dst + (size_t)r0 * d.n_vocab; p.ldc = d.n_vocab; p.n_valid = d.n_vocab;
+            if (launch_gemm_skinny(p, s)) return 2;
+        }
+        return 0;
+    }
+
+    // block prefill: logits for the positions logits_from .. L - 1 of every utterance only; the others are left untouched.  The rows of
+    // one utterance are consecutive in x and in `logits`; a few positions per utterance (logits_from = sot_index: three) are gathered
+    // over as many utterances as fill one weight-streaming launch, so the vocabulary matrix is read once per SKINNY_MAX_M rows
+    int end_prefill(hipStream_t s) {
+        const wm_dims& d = e->dims;
+        const int n = L - logits_from;
+        h16* out = (h16*)io->logits;
+        if (n == L) return logits_rows(w.x, M, out, s);
+        if (n * 2 > SKINNY_MAX_M) {
+            for (int b = 0; b < B; ++b)
+                if (int rc = logits_rows(w.x + ((size_t)b * L + logits_from) * C, n, out + ((size_t)b * L + logits_from) * d.n_vocab, s)) return rc;
+            return 0;
+        }
+        const int ub = SKINNY_MAX_M / n;
+        for (int b0 = 0; b0 < B; b0 += ub) {
+            const int nb = (B - b0) < ub ? (B - b0) : ub;
+            if (launch_copy_rows2d(w.ctx, (long)n * C, w.x + ((size_t)b0 * L + logits_from) * C, (long)L * C, (long)n * C, nb, s)) return 2;
+            if (int rc = logits_rows(w.ctx, nb * n, w.logit_stage, s)) return rc;
+            if (launch_copy_rows2d(out + ((size_t)b0 * L + logits_from) * d.n_vocab, (long)L * d.n_vocab, w.logit_stage, (long)n * d.n_vocab,
+                                   (long)n * d.n_vocab, nb, s)) return 2;
         }
         return 0;
     }
@@ -1206,6 +1266,44 @@ static int decoder_step(const wm_engine* e, const wm_decoder_io* io, int cross_g
 }
 
 int wm_decoder_step(const wm_engine* e, const wm_decoder_io* io, wm_stream_t stream) { return decoder_step(e, io, 0, nullptr, stream); }
+
+// Block prefill: the whole start block in ONE pass of the launch-per-kernel sequence at M = batch * n_new rows (the Linear forms GroupStep
+// picks for that M), with attn_prefill.hip's two kernels in place of the decode attention.  Every refusal comes before the first launch.
+size_t wm_decoder_prefill_workspace_bytes(const wm_engine* e, int batch, int n_new) {
+    if (!e || e->kind != WM_ENGINE_DECODER || batch < 1 || n_new < 1 || n_new > e->dims.n_text_ctx) return 0;
+    return carve_decoder(e, batch, n_new, nullptr, 1, true).total;
+}
+
+int wm_decoder_prefill(const wm_engine* e, const wm_prefill_io* pio, wm_stream_t stream_) {
+    WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_prefill: not a decoder engine");
+    WM_REQUIRE(pio, "wm_decoder_prefill: null argument");
+    const wm_decoder_io* io = &pio->io;
+    const int L = io->n_new;
+    WM_REQUIRE(!e->i8cross(), "wm_decoder_prefill: engines with int8 cross K/V are not supported (the block kernels read fp16 cross K/V)");
+    WM_REQUIRE(io->batch >= 1 && L >= 1, "wm_decoder_prefill: bad batch/n_new (%d, %d)", io->batch, L);
+    WM_REQUIRE(L <= e->dims.n_text_ctx, "wm_decoder_prefill: n_new=%d exceeds n_text_ctx=%d", L, e->dims.n_text_ctx);
+    WM_REQUIRE(io->n_past == 0, "wm_decoder_prefill: n_past=%d: the block goes on an empty cache (n_past must be 0)", io->n_past);
+    WM_REQUIRE(!io->n_past_dev, "wm_decoder_prefill: a device step counter (n_past_dev) is not supported");
+    WM_REQUIRE(!io->qkv_amax, "wm_decoder_prefill: the calibration hook (qkv_amax) is not supported");
+    WM_REQUIRE(io->present, "wm_decoder_prefill: present buffers are missing");
+    for (int i = 0; i < e->dims.n_text_layer; ++i) {
+        WM_REQUIRE(io->present[i], "wm_decoder_prefill: present[%d] is null", i);
+        WM_REQUIRE(io->cross && io->cross[i], "wm_decoder_prefill: cross[%d] is null", i);
+    }
+    WM_REQUIRE(io->present_capacity >= L, "wm_decoder_prefill: present capacity %d < n_new = %d", io->present_capacity, L);
+    WM_REQUIRE(pio->logits_from >= 0 && pio->logits_from < L, "wm_decoder_prefill: logits_from=%d is outside 0 .. n_new - 1 = %d", pio->logits_from, L - 1);
+    hipStream_t s = (hipStream_t)stream_;
+    GroupStep g;
+    g.prefill = true; g.logits_from = pio->logits_from;
+    if (int rc = g.init(e, io, s, false)) return rc;
+    if (g.begin(s)) return 2;
+    for (int i = 0; i < e->dims.n_text_layer; ++i) {
+        if (g.pre_cross(i, s)) return 2;
+        if (g.cross(i, s)) return 2;
+        if (g.post_cross(i, s)) return 2;
+    }
+    return g.end_prefill(s);
+}
 
 int wm_decoder_step_group(const wm_engine* e, const wm_decoder_group_io* gio, wm_stream_t stream) {
     WM_REQUIRE(gio, "wm_decoder_step_group: null argument");
@@ -1720,6 +1818,28 @@ int wm_attn_decode_self(const float* qkv, int B, int L, int T, int H, const void
     p.int8_kv = int8_kv; p.kv_scale = kv_scale; p.out = (h16*)out; p.ldo = H * 64;
     p.waves = self_attn_waves(B * L);
     return launch_attn_self(p, (hipStream_t)stream);
+}
+
+int wm_attn_prefill_self(const float* qkv, int B, int L, int H, void* cache, int cap, int int8_kv, float kv_scale, void* out,
+                         const int32_t* row_start, const int32_t* live_rows, wm_stream_t stream) {
+    WM_REQUIRE(qkv && cache && out, "wm_attn_prefill_self: null argument");
+    AttnSelfParams p{};
+    p.part = qkv; p.ksplit = 1; p.ldp = 3 * H * 64; p.bias = nullptr;
+    p.B = B; p.L = L; p.T = 0; p.H = H;
+    p.present = cache; p.present_cap = cap; p.present_bstride = (long)2 * H * cap * 64;
+    p.past = cache; p.past_cap = cap; p.past_bstride = p.present_bstride;
+    p.int8_kv = int8_kv; p.kv_scale = kv_scale; p.out = (h16*)out; p.ldo = H * 64;
+    p.row_start = row_start; p.live = live_rows;
+    return launch_attn_prefill_self(p, (hipStream_t)stream);
+}
+
+int wm_attn_prefill_cross(const float* q, int B, int L, int H, int Tk, const void* kv, void* out, const int32_t* live_rows, wm_stream_t stream) {
+    WM_REQUIRE(q && kv && out, "wm_attn_prefill_cross: null argument");
+    AttnCrossParams p{};
+    p.part = q; p.ksplit = 1; p.ldp = H * 64; p.bias = nullptr;
+    p.B = B; p.L = L; p.H = H; p.Tk = Tk; p.kv = (const h16*)kv; p.kv_bstride = (long)2 * H * Tk * 64;
+    p.out = (h16*)out; p.ldo = H * 64; p.live = live_rows;
+    return launch_attn_prefill_cross(p, (hipStream_t)stream);
 }
 
 int wm_attn_decode_self_rows(const float* qkv, int B, int L, int T, int H, void* cache, int cap, int int8_kv, float kv_scale, void* out,

@@ -167,6 +167,7 @@ struct EmbedParams {
     const int32_t* row_start; int T;
 };
 int launch_embed(const EmbedParams& p, hipStream_t stream);
+int launch_copy_rows2d(h16* dst, long dpitch, const h16* src, long spitch, long width, int height, hipStream_t stream);      // fp16 elements; row r: src + r * spitch -> dst + r * dpitch
 
 int launch_mel_transpose_pad(const h16* mel, int B, int n_mels, int T, h16* out /*[B][T+2][n_mels]*/,
                              hipStream_t stream);
@@ -244,6 +245,14 @@ constexpr int CROSS_GROUP_MAX = 8;           // queries one K/V walk serves (= B
 // (bit-identical with it on or off: test_cross_attention_v_skip_*, and at the key-range edges tests/test_gpu_attn_decode_contract.py)
 constexpr int CROSS_V_SKIP_DEFAULT = 1;      // measured: profiles/r4e_* (diffuse attention: no slower; peaked: FETCH_SIZE falls with the skipped rows)
 int launch_attn_cross(const AttnCrossParams& p, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+
+// ---------------------------------------------------------------- attn_prefill.hip
+// Block prefill (wm_decoder_prefill): L = 1 .. n_text_ctx queries per utterance in one launch.  Both take the decode kernels' parameter
+// blocks and read what applies: self -- part / ksplit / ldp / part_sstride / bias, B, L, H, T (must be 0), present (appended in
+// place, slots 0 .. L - 1), int8_kv / kv_scale, out / ldo, live, row_start; cross -- part ... bias, B, L, H, Tk, kv (fp16 only),
+// out / ldo, live.  The contract stands at the top of attn_prefill.hip.
+int launch_attn_prefill_self(const AttnSelfParams& p, hipStream_t stream);
+int launch_attn_prefill_cross(const AttnCrossParams& p, hipStream_t stream);
 
 // ---------------------------------------------------------------- greedy.hip
 struct GreedyParams {

@@ -275,6 +275,23 @@ int launch_embed(const EmbedParams& p, hipStream_t stream) {
     return 0;
 }
 
+// ---- `height` rows of `width` fp16 elements, row r from src + r * spitch to dst + r * dpitch (the logits rows the block prefill keeps:
+// a vocabulary row is 2 * n_vocab bytes, no multiple of 16, so the copy goes element by element).  One row per blockIdx.y.
+__global__ __launch_bounds__(256) void copy_rows2d_kernel(h16* dst, long dpitch, const h16* src, long spitch, long width) {
+    const h16* s = src + (long)blockIdx.y * spitch;
+    h16* d = dst + (long)blockIdx.y * dpitch;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < width; c += (long)gridDim.x * 256) d[c] = s[c];
+}
+
+int launch_copy_rows2d(h16* dst, long dpitch, const h16* src, long spitch, long width, int height, hipStream_t stream) {
+    WM_REQUIRE(dst && src && width >= 1 && height >= 1 && height <= 65535 && dpitch >= width && spitch >= width, "copy_rows2d: bad arguments");
+    const long blocks = (width + 255) / 256;
+    hipLaunchKernelGGL(copy_rows2d_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024), (unsigned)height), dim3(256), 0, stream, dst, dpitch, src,
+                       spitch, width);
+    WM_LAUNCH_CHECK(stream, "copy_rows2d");
+    return 0;
+}
+
 // ---- mel [B][n_mels][T] (channel-major, what run.py hands over) -> token-major [B][T+2][n_mels]
 // with one zero row before and after each utterance, so that conv1 (k3, s1, p1) is a GEMM over a
 // strided view of this buffer.

@@ -377,7 +377,7 @@ def right_aligned_rows(prompts: Sequence[Sequence[int]], sot_sequence: Sequence[
 class WhisperDecoding:
     def __init__(self, engine_dir, only_torch: bool = False, vocab_path: Optional[str] = None,
                  options: Optional[DecodingOptions] = None, row_prompts: bool = False, shared_cross_kv: bool = False,
-                 fallback_best_of: Optional[int] = None):
+                 fallback_best_of: Optional[int] = None, block_prefill: bool = False):
         """`shared_cross_kv` (opt-in): the n_group candidates of an utterance (beams, best_of samples) read ONE copy of its
         cross-attention K/V (wm_decoder_group_io::cross_group) instead of a copy each: the cross K/V are projected once from the
         un-repeated features, held once per utterance and streamed once per utterance and token step.  Device loop only; not
@@ -391,7 +391,17 @@ class WhisperDecoding:
         sample_len is min(sample_len, n_text_ctx - L0) -- a row with a full prompt is cut exactly where upstream cuts it, a row
         with a short or no prompt loses at most len(sot_sequence) tokens against upstream's n_text_ctx // 2 (and pays for a
         prefill of L0 tokens).  Device loop only (greedy, temperature, best_of, beam search); not with `options.prompt` /
-        `options.prefix`, not with `cu_partition`; word_timestamps stays prompt-free, as upstream."""
+        `options.prefix`, not with `cu_partition`; word_timestamps stays prompt-free, as upstream.
+        `block_prefill` (opt-in): every start block longer than 4 tokens -- the L0 tokens of a `row_prompts` instance, an
+        `options.prompt` / `options.prefix` block -- runs through wm_decoder_prefill, ONE pass over the block with logits from
+        `sot_index` on, instead of ceil(L0 / 4) passes of wm_decoder_step that each stream the weights and the cross K/V again; the call
+        is captured and replayed like the 3-token prefill.  Inside the block the attention is un-quantised whatever the cache type
+        (what upstream computes; the 4-token passes see earlier prompt tokens through their int8 codes), so with an int8 KV cache the
+        logits differ from the default's within the int8-KV bound.  Start blocks of up to 4 tokens, the language pass, the forced
+        pass of word_timestamps and every decode step are unchanged.  Not with int8 cross K/V engines, not with `cu_partition`.
+        It pays at every row count measured (scripts/bench_prompts.py, large-v2 int8, L0 = 227): time to the first
+        token 117.6 -> 5.4 ms at one row, 202.9 -> 17.8 ms at 8, 613.3 -> 91.9 ms at 64 with full prompts, and as much without prompts;
+        no row count was found where it is not lower.  A start block of up to 4 tokens never takes it."""
         engine_dir = Path(engine_dir)
         self.decoder_config = None
         self.cross_attn_config = None
@@ -439,6 +449,9 @@ class WhisperDecoding:
         self.sample_begin: int = len(self.initial_tokens)
         self.use_int8_kv_cache = self.decoder_config['use_int8_kv_cache']
         self.use_int8_cross_kv = bool(self.decoder_config.get('use_int8_cross_kv', False))     # opt-in, beyond the reference
+        self.block_prefill = bool(block_prefill)
+        if self.block_prefill and self.use_int8_cross_kv:
+            raise ValueError("block_prefill: engines with int8 cross K/V are not supported (wm_decoder_prefill reads fp16 cross K/V)")
 
         pe = np.load(engine_dir / 'positional_embedding.npy')
         self.positional_embedding = torch.tensor(pe)
@@ -1343,6 +1356,8 @@ class WhisperDecoding:
         n_micro, bounds = self._groups(n_batch)
         if self.cu_partition and n_micro > 1 and self.beam:
             raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
+        if self.cu_partition and self.block_prefill:
+            raise ValueError("block_prefill is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
         if self.cu_partition and n_micro > 1 and self.row_prompts:
             raise ValueError("row_prompts is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
         if self.row_prompts:
@@ -1419,7 +1434,9 @@ class WhisperDecoding:
                     # GPU needs 1.7 at one utterance; with the language pass 9.5 ms per batch of 2 x 8)
                     pkey = (n_micro, slot, use_live, 'prefill', L0, shared) + bkey
 
-                    def issue_prefill(gr=gr, lo=lo, hi=hi, sm=sm, slot=slot):
+                    block = self.block_prefill and L0 > 4       # one pass over the whole start block (wm_decoder_prefill), logits from sot_index on
+
+                    def issue_prefill(gr=gr, lo=lo, hi=hi, sm=sm, slot=slot, block=block):
                         if G > 1:
                             # shared cross K/V: the candidates of an utterance begin with the same tokens over the same audio, so ONE row
                             # per utterance is prefilled (group 1, on the utterances' cross K/V and the group's first cache rows: what
@@ -1427,13 +1444,21 @@ class WhisperDecoding:
                             a_lo, a_hi = lo // G, hi // G
                             n_u = a_hi - a_lo
                             with torch.cuda.stream(streams[slot]):
-                                sess.decoder_step(st['tokens'][lo:hi:G, :L0], pos[0:L0], gr['cross'], None, cap, [t[:n_u] for t in gr['kv']], cap,
-                                                  st['logits_u'][a_lo:a_hi], 0, sm, slot=slot, not_alone=shared,
-                                                  row_start=st['row_start_u'][a_lo:a_hi] if self.row_prompts else None)
+                                if block:
+                                    sess.decoder_prefill(st['tokens'][lo:hi:G, :L0], pos[0:L0], gr['cross'], [t[:n_u] for t in gr['kv']], cap,
+                                                         st['logits_u'][a_lo:a_hi], sm, self.sot_index, slot=slot,
+                                                         row_start=st['row_start_u'][a_lo:a_hi] if self.row_prompts else None)
+                                else:
+                                    sess.decoder_step(st['tokens'][lo:hi:G, :L0], pos[0:L0], gr['cross'], None, cap, [t[:n_u] for t in gr['kv']], cap,
+                                                      st['logits_u'][a_lo:a_hi], 0, sm, slot=slot, not_alone=shared,
+                                                      row_start=st['row_start_u'][a_lo:a_hi] if self.row_prompts else None)
                                 for t in gr['kv']:
                                     first = t[:n_u, :, :, :L0].clone()
                                     t.view(n_u, G, *t.shape[1:])[:, :, :, :, :L0] = first[:, None]
                                 gr['logits'].view(n_u, G, L0, V)[:] = st['logits_u'][a_lo:a_hi, None]
+                        elif block:
+                            sess.decoder_prefill(gr['tokens'][:, :L0], pos[0:L0], gr['cross'], gr['kv'], cap, gr['logits'], sm, self.sot_index,
+                                                 slot=slot, live_rows=gr['live'], row_start=gr['row_start'])
                         else:
                             sess.decoder_step(gr['tokens'][:, :L0], pos[0:L0], gr['cross'], None, cap, gr['kv'], cap,
                                               gr['logits'], 0, sm, slot=slot, live_rows=gr['live'], not_alone=shared, row_start=gr['row_start'])
@@ -1444,7 +1469,7 @@ class WhisperDecoding:
                             st['graphs'][pkey].replay()
                     else:
                         issue_prefill()
-                        if use_graph and self.graph_prefill and L0 <= 4:        # (longer start sequences run as 4-token passes with copies between them: eager)
+                        if use_graph and self.graph_prefill and (L0 <= 4 or block):        # (longer start sequences run as 4-token passes with copies between them: eager -- unless the block prefill takes them in one pass)
                             self._capture(st, pkey, streams[slot], issue_prefill)
                 elif use_graph and gkey in st['graphs']:
                     if i == 1 or st['counters'][gkey + ('fresh',)]:

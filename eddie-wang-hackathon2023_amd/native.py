@@ -87,6 +87,7 @@ EXPORTS = (
     "wm_forced_probs",
     "wm_section_cuts_workspace_bytes", "wm_section_cuts",
     "wm_step_finish_group", "wm_attn_cross_group_ex", "wm_decoder_step_group",
+    "wm_decoder_prefill_workspace_bytes", "wm_decoder_prefill", "wm_attn_prefill_self", "wm_attn_prefill_cross",
 )
 
 
@@ -152,6 +153,11 @@ class WmDecoderIO(C.Structure):
 class WmDecoderGroupIO(C.Structure):
     """wm_decoder_group_io (include/whisper_mi355.h): a decoder call whose rows share cross K/V in groups of `cross_group`."""
     _fields_ = [("io", WmDecoderIO), ("cross_group", C.c_int32), ("live_groups", C.c_void_p)]
+
+
+class WmPrefillIO(C.Structure):
+    """wm_prefill_io (include/whisper_mi355.h): a whole start block on an empty cache, logits from position `logits_from` on."""
+    _fields_ = [("io", WmDecoderIO), ("logits_from", C.c_int32)]
 
 
 class WmGemvIO(C.Structure):
@@ -346,6 +352,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_decoder_workspace_bytes.restype = sz
     lib.wm_decoder_step.argtypes = [vp, C.POINTER(WmDecoderIO), vp]
     lib.wm_decoder_step_group.argtypes = [vp, C.POINTER(WmDecoderGroupIO), vp]
+    lib.wm_decoder_prefill_workspace_bytes.restype = C.c_size_t
+    lib.wm_decoder_prefill_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.wm_decoder_prefill.argtypes = [vp, C.POINTER(WmPrefillIO), vp]
+    lib.wm_attn_prefill_self.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.c_float, vp, vp, vp, vp]
+    lib.wm_attn_prefill_cross.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.wm_greedy_step.argtypes = [C.POINTER(WmGreedyIO), vp]
     lib.wm_gemm.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, sz, vp]
     lib.wm_conv1d_gelu.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp]

@@ -215,7 +215,7 @@ class Session(object):
                         n_past_dev: Optional[torch.Tensor] = None, n_new: Optional[int] = None,
                         live_rows: Optional[torch.Tensor] = None, not_alone: bool = False,
                         row_start: Optional[torch.Tensor] = None, cross_group: int = 1,
-                        live_groups: Optional[torch.Tensor] = None) -> WmDecoderIO:
+                        live_groups: Optional[torch.Tensor] = None, prefill: bool = False) -> WmDecoderIO:
         """The wm_decoder_io of one call.  tokens int32 [B, L] (any row stride: a column window of a wider
         buffer works); past/present per layer [B,2,H,capacity,64]; present may be the same tensors as past
         (in-place append).  `cross_group` = G > 1: rows a * G .. a * G + G - 1 share row a of `cross` [B / G, ...] (candidate groups,
@@ -236,7 +236,10 @@ class Session(object):
             raise native.WmError(f"decoder step: {b} rows are not a multiple of cross_group = {cross_group}")
         if logits.shape[0] != b:
             raise native.WmError(f"decoder step: logits hold {logits.shape[0]} utterances, tokens hold {b}")
-        ws = self._workspace(("dec", b, l, slot), lib.wm_decoder_workspace_bytes(self._engine.handle, b, l))
+        if prefill:                    # the io of a wm_prefill_io: the block prefill's own workspace, linear in b * l
+            ws = self._workspace(("prefill", b, l, slot), lib.wm_decoder_prefill_workspace_bytes(self._engine.handle, b, l))
+        else:
+            ws = self._workspace(("dec", b, l, slot), lib.wm_decoder_workspace_bytes(self._engine.handle, b, l))
         io = WmDecoderIO()
         io.batch, io.n_new, io.n_past = b, l, n_past
         io.tokens, io.positional_embedding = tokens.data_ptr(), pos.data_ptr()
@@ -289,6 +292,17 @@ class Session(object):
         io = self.make_decoder_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
                                   qkv_amax, slot, n_past_dev, n_new, live_rows, not_alone, row_start)
         check(self._engine.lib.wm_decoder_step(self._engine.handle, C.byref(io), stream), "wm_decoder_step")
+
+    def decoder_prefill(self, tokens, pos, cross, present, capacity, logits, stream: int, logits_from: int, slot: int = 0,
+                        live_rows=None, row_start=None):
+        """wm_decoder_prefill: the whole block tokens int32 [B, L] (L = 1 .. n_text_ctx) on the EMPTY cache `present` (appended in place,
+        slots 0 .. L - 1) in one pass; logits fp16 [B, L, V] are written for the positions logits_from .. L - 1 only."""
+        pio = native.WmPrefillIO()
+        pio.io = self.make_decoder_io(tokens, pos, cross, None, 0, present, capacity, logits, 0, None, slot, None, None, live_rows, False,
+                                      row_start, prefill=True)
+        pio.logits_from = int(logits_from)
+        pio._keep = pio.io
+        check(self._engine.lib.wm_decoder_prefill(self._engine.handle, C.byref(pio), stream), "wm_decoder_prefill")
 
     def decoder_step_tap(self, tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past, stream: int,
                          q_tape: torch.Tensor, heads, slot: int = 0):

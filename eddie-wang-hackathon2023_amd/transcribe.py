@@ -394,6 +394,8 @@ def parse_arguments(argv=None):
     parser.add_argument('--rows', type=int, default=None, help='rows of a decoder call (default: min(files, what fits))')
     parser.add_argument('--condition_on_previous_text', default=False, action='store_true',
                         help="decode every window with the file's text so far as its prompt (upstream's default; off here)")
+    parser.add_argument('--block_prefill', default=False, action='store_true',
+                        help='run start blocks of more than 4 tokens (a prompt per row) in one pass (WhisperDecoding(block_prefill=True)); implies nothing else')
     parser.add_argument('--initial_prompt', type=str, default=None, help="text in front of every file's first window: names, spelling, style")
     parser.add_argument('--word_timestamps', default=False, action='store_true',
                         help='print "start-end word (probability)" lines under every segment (cross-attention alignment + DTW on the device)')
@@ -418,13 +420,15 @@ def build_decoding(args, engine_dir, prompted: bool) -> WhisperDecoding:
     if args.beam_size is not None:
         options = DecodingOptions(language=args.language, beam_size=args.beam_size, patience=args.patience)
         return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,
-                               fallback_best_of=args.best_of if args.best_of is not None else 1)
+                               fallback_best_of=args.best_of if args.best_of is not None else 1, block_prefill=args.block_prefill)
     if args.patience is not None:
         raise ValueError("--patience needs --beam_size")
     if args.best_of is not None:
         options = DecodingOptions(language=args.language, best_of=args.best_of, temperature=float(args.temperature[0]))
-        return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True)
-    return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language), row_prompts=prompted)
+        return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,
+                               block_prefill=args.block_prefill)
+    return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language), row_prompts=prompted,
+                           block_prefill=args.block_prefill)
 
 
 def main(args) -> List[dict]:

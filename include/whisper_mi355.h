@@ -66,7 +66,9 @@ typedef struct wm_dims {
  *      (still 8: entries and structs of their own, no existing struct or signature changed) wm_decoder_step_group / wm_decoder_group_io,
  *      wm_step_finish_group, wm_attn_cross_group_ex
  *      (still 8: an entry only) wm_forced_probs
- *      (still 8: entries only) wm_section_cuts, wm_section_cuts_workspace_bytes */
+ *      (still 8: entries only) wm_section_cuts, wm_section_cuts_workspace_bytes
+ *      (still 8: entries and a struct of their own, no existing struct or signature changed) wm_decoder_prefill / wm_prefill_io,
+ *      wm_decoder_prefill_workspace_bytes; test-only entries wm_attn_prefill_self, wm_attn_prefill_cross */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -212,6 +214,32 @@ typedef struct wm_decoder_group_io {
     const int32_t* live_groups;
 } wm_decoder_group_io;
 int wm_decoder_step_group(const wm_engine* e, const wm_decoder_group_io* gio, wm_stream_t stream);
+
+/* ---- block prefill: a whole start block in ONE pass (added within ABI 8: a struct and entries of their own) ----
+ * wm_decoder_step runs a block of more than 4 tokens as 4-token passes over the growing cache: a 227-token block (a prompt per row) is
+ * 57 passes, each of which streams every decoder weight and every row's cross K/V again.  wm_decoder_prefill runs the block -- n_new = L
+ * tokens, 1 .. n_text_ctx, on an EMPTY cache (n_past must be 0) -- through the launch-per-kernel layer sequence once, at batch * L rows
+ * (the Linear forms the step picks for that many rows), with two attention kernels of its own (csrc/attn_prefill.hip):
+ *   - self-attention is causal inside the block over the block's own UN-QUANTISED k / v, whatever the cache type -- what the reference
+ *     computes for a block fed whole; the 4-token passes of wm_decoder_step see the earlier tokens of the same block through their int8
+ *     codes when the engine has WM_FLAG_INT8_KV, so the two agree within the int8-KV bound, not bit for bit.  Every slot 0 .. L - 1 is
+ *     appended to present[i] in place (fp16 rows, or int8 codes), pad slots included;
+ *   - io.row_start and io.live_rows behave as in wm_decoder_step: a query in a pad slot yields zeros in the self-attention, its logits
+ *     are finite and meaningless; rows that live_rows does not name are not read by the attention kernels and their cache is not
+ *     written -- their rows of `logits` (from logits_from on) ARE written, with unspecified values (computed from whatever the workspace held);
+ *   - io.logits keeps wm_decoder_step's layout, fp16 [batch, L, n_vocab], but only positions logits_from .. L - 1 of every utterance are
+ *     written (the final LayerNorm and the vocabulary product run over batch * (L - logits_from) rows); positions below are untouched;
+ *   - io.past / past_capacity are not read; workspace: wm_decoder_prefill_workspace_bytes(batch, n_new), linear in batch * n_new; no
+ *     allocation, no synchronisation: the call can be captured into a hipGraph; it never takes a one-launch form.
+ * rc 1 (nothing launched) for: n_past != 0, n_past_dev or qkv_amax set, present buffers missing or present_capacity < L,
+ * L > n_text_ctx, logits_from outside 0 .. L - 1, an engine with WM_FLAG_INT8_CROSS_KV.  A following wm_decoder_step continues on
+ * the cache with n_past = L.                                                                                                          */
+typedef struct wm_prefill_io {
+    wm_decoder_io io;        /* n_new = L, 1 .. n_text_ctx; n_past must be 0 */
+    int32_t logits_from;     /* 0 .. L-1: logits are written for positions logits_from .. L-1 only */
+} wm_prefill_io;
+size_t wm_decoder_prefill_workspace_bytes(const wm_engine* e, int batch, int n_new);
+int wm_decoder_prefill(const wm_engine* e, const wm_prefill_io* io, wm_stream_t stream);
 
 /* The same step for n_groups (<= 8) independent utterance groups at once, scheduled for the chip:
  * group g's latency-bound kernels (weight-streaming GEMMs, row kernels, self-attention) are enqueued on
@@ -690,6 +718,13 @@ int wm_attn_decode_self(const float* qkv, int B, int L, int T, int H, const void
 /* The same in place (past == present == cache, capacity cap) with right-aligned rows and / or a live-row list, as wm_decoder_step
  * launches it: row_start int32 [B] or NULL (wm_decoder_io::row_start), live_rows int32 [1 + B] or NULL (wm_decoder_io::live_rows:
  * rows not listed are neither read nor written).  L <= 4.                                                                          */
+/* Kernel-level test entries of the block prefill (csrc/attn_prefill.hip), fp32 rows in, like wm_attn_decode_self / _cross.
+ * self: qkv fp32 [B * L, 3 * H * 64] on an empty cache [B, 2, H, cap, 64] (appended in place: slots 0 .. L - 1), out fp16 [B * L, H * 64];
+ * cross: q fp32 [B * L, H * 64] over kv fp16 [B, 2, H, Tk, 64].  row_start int32 [B] or NULL, live_rows int32 [1 + B] or NULL. */
+int wm_attn_prefill_self(const float* qkv, int B, int L, int H, void* cache, int cap, int int8_kv, float kv_scale, void* out,
+                         const int32_t* row_start, const int32_t* live_rows, wm_stream_t stream);
+int wm_attn_prefill_cross(const float* q, int B, int L, int H, int Tk, const void* kv, void* out, const int32_t* live_rows,
+                          wm_stream_t stream);
 int wm_attn_decode_self_rows(const float* qkv, int B, int L, int T, int H, void* cache, int cap, int int8_kv, float kv_scale,
                              void* out, const int32_t* row_start, const int32_t* live_rows, wm_stream_t stream);
 /* q = sat_s8(rne(x * inv_scale)) (quantizeTensorPlugin / attention.py:340-348). */

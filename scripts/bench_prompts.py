@@ -2,7 +2,8 @@
 A main_loop call of an instance built with row_prompts=True (every row carries a prompt: a prefill of
 L0 = n_text_ctx // 2 + len(sot_sequence) tokens in 4-token passes, token steps that never take a one-launch form) beside the
 same call of a plain instance on the same engine, at 1, 8 and 64 rows; the prefill (up to the first sampled token) and the
-steps behind it are timed apart.
+steps behind it are timed apart.  A third column is the same row_prompts call on an instance built with block_prefill=True (the L0
+tokens in ONE pass, wm_decoder_prefill), without prompts and with full prompts, on the same rows.
       python scripts/bench_prompts.py [tokens=32] [rows=1,8,64] [engine_dir]
 Without an engine directory: the large-v2 engines `bench.py --engine-cache /tmp/wm_bench_engines` keeps when they exist, else
 a `tiny`-shaped engine with seeded random weights built into a temporary directory."""
@@ -68,10 +69,17 @@ for n in ROWS:
         dec.set_prompts(prompts)
         out[name] = timed(dec, xa)
     steps = min(TOKENS, dec.sample_len)
+    del dec
+    dec = WhisperDecoding(eng, row_prompts=True, block_prefill=True, options=DecodingOptions(sample_len=TOKENS, language="en"))
+    for name, prompts in (("block_no_prompt", [[] for _ in range(n)]), ("block_full_prompt", full)):
+        dec.set_prompts(prompts)
+        out[name] = timed(dec, xa)
     report["rows"][n] = dict(L0=dec.sample_begin, steps=steps, plain_prefill_ms=plain_pre, plain_call_ms=plain_all,
                              **{f"{k}_prefill_ms": v[0] for k, v in out.items()}, **{f"{k}_call_ms": v[1] for k, v in out.items()})
     print(f"{shape or eng}, {n} rows, {steps} tokens: plain call {plain_all:.1f} ms (first token after {plain_pre:.2f} ms); "
           f"row_prompts (L0 = {dec.sample_begin}) without prompts {out['no_prompt'][1]:.1f} ms (first token after {out['no_prompt'][0]:.2f} ms), "
-          f"with {dec.prompt_capacity}-token prompts {out['full_prompt'][1]:.1f} ms (first token after {out['full_prompt'][0]:.2f} ms)")
+          f"with {dec.prompt_capacity}-token prompts {out['full_prompt'][1]:.1f} ms (first token after {out['full_prompt'][0]:.2f} ms); "
+          f"block_prefill without prompts {out['block_no_prompt'][1]:.1f} ms (first token after {out['block_no_prompt'][0]:.2f} ms), "
+          f"with prompts {out['block_full_prompt'][1]:.1f} ms (first token after {out['block_full_prompt'][0]:.2f} ms)")
     del dec
 print(json.dumps(report))
