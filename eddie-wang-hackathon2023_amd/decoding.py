@@ -374,6 +374,178 @@ def right_aligned_rows(prompts: Sequence[Sequence[int]], sot_sequence: Sequence[
     return rows, starts
 
 
+# ---- the device loop's schedule: streams, the "alone" decision, graph keys (pure: tests/test_decode_plan_cpu.py) ---------------
+
+def fork(main, streams) -> None:
+    """Every stream of `streams` waits for what `main` holds so far."""
+    for s in streams:
+        s.wait_stream(main)
+
+
+def join(main, streams) -> None:
+    """`main` waits for what every stream of `streams` holds so far."""
+    for s in streams:
+        main.wait_stream(s)
+
+
+def steps_side_by_side(n_micro: int, sequential: bool, force_not_alone: bool) -> bool:
+    """The `not_alone` of every launch of a pass: stream-parallel groups have the steps of two groups in flight at once, so none of
+    them may take a one-launch form (two 256-workgroup launches side by side can each hold half of the chip and wait for the other
+    half: ADVICE r5, whisper_mi355.h `not_alone`).  `force_not_alone`: bench.py's probes step the groups one after the other but
+    must run the kernels of the parallel schedule."""
+    return (n_micro > 1 and not sequential) or force_not_alone
+
+
+def groups_run_alone(bounds: Sequence[Tuple[int, int]], n_micro: int, sequential: bool, force_not_alone: bool) -> bool:
+    """May a group of this pass take the one-launch step (csrc/gemv_chain.hip)?  Groups of up to eight rows stepped one at a time."""
+    return (n_micro == 1 or sequential) and not force_not_alone and any(hi - lo <= 8 for lo, hi in bounds)
+
+
+def call_key(beam: bool, ignore_eot: bool, cross_group: int, temperature: float, own_temperature: float) -> tuple:
+    """What of a main_loop call its captured graphs bake in, as the tail of their keys."""
+    key = ('beam', bool(ignore_eot)) if beam else ()         # (ignore_eot is an argument of the captured beam step)
+    if cross_group > 1:
+        key += (('cross_group', cross_group),)
+    if temperature != own_temperature:
+        key += (('temperature', temperature),)               # (so is the temperature: a per-call one has graphs of its own)
+    return key
+
+
+def step_key(n_micro: int, slot: int, use_live: bool, bkey: tuple = ()) -> tuple:
+    return (n_micro, slot, use_live) + bkey
+
+
+def prefill_key(n_micro: int, slot: int, use_live: bool, L0: int, not_alone: bool, bkey: tuple = ()) -> tuple:
+    return (n_micro, slot, use_live, 'prefill', L0, not_alone) + bkey
+
+
+def language_key(n_micro: int, slot: int, not_alone: bool) -> tuple:
+    return (n_micro, slot, 'lang', not_alone)
+
+
+def partition_key(n_micro: int) -> tuple:
+    return ('partition', n_micro)
+
+
+@dataclass
+class _Call:
+    """What the groups of one device-loop call share."""
+    st: dict
+    cross: list
+    L0: int
+    n_micro: int
+    use_live: bool
+    not_alone: bool
+    beam: bool              # this call's decoder (fallback_best_of: samples above temperature 0)
+    ignore_eot: bool
+    temperature: float
+    bkey: tuple
+    use_graph: bool
+    block: bool             # one pass over the whole start block (wm_decoder_prefill), logits from sot_index on
+    graph_prefill: bool     # (longer start sequences run as 4-token passes with copies between them: eager -- unless `block`)
+
+
+class _Group:
+    """One utterance group of a device-loop call: rows [lo, hi) of the batch state on a stream of their own, and the group's step in
+    its three forms -- `prefill`, `step`, `step_counted` -- each "decoder launch, token step, step finish"."""
+
+    def __init__(self, dec: "WhisperDecoding", call: _Call, slot: int, lo: int, hi: int, stream):
+        st, G, n_micro = call.st, dec._cross_group(), call.n_micro
+        self.dec, self.call, self.slot, self.lo, self.hi = dec, call, slot, lo, hi
+        self.stream, self.sm, self.active = stream, stream.cuda_stream, True
+        self.kv = [t[lo:hi] for t in st['kv']]
+        self.cross = [t[lo // G:hi // G] for t in call.cross]
+        self.live_groups = dec._live_groups(st, n_micro, slot, lo, hi) if call.use_live and G > 1 else None
+        self.logits, self.tokens, self.done = st['logits'][lo:hi], st['tokens'][lo:hi], st['done'][lo:hi]
+        self.live = dec._live_list(st, n_micro, slot, lo, hi) if call.use_live else None
+        self.row_start = st['row_start'][lo:hi] if dec.row_prompts else None
+        if dec.beam:       # the group's cache rows per layer as a device-resident pointer table (wm_kv_reorder; stable like the buffers)
+            if (n_micro, slot) not in st['kv_tables']:
+                st['kv_tables'][(n_micro, slot)] = torch.tensor([t.data_ptr() for t in self.kv], dtype=torch.int64, device=self.done.device)
+            self.kv_table = st['kv_tables'][(n_micro, slot)]
+        self.step_key = step_key(n_micro, slot, call.use_live, call.bkey)
+        self.fresh_key = self.step_key + ('fresh',)
+        self.prefill_key = prefill_key(n_micro, slot, call.use_live, call.L0, call.not_alone, call.bkey)
+
+    def prefill(self, L0: int) -> None:
+        """The L0 start tokens on the empty cache, and the first token step."""
+        dec, st, G = self.dec, self.call.st, self.dec._cross_group()
+        if G > 1:
+            # shared cross K/V: the candidates of an utterance begin with the same tokens over the same audio, so ONE row per
+            # utterance is prefilled (group 1, on the utterances' cross K/V and the group's first cache rows: what each candidate's
+            # row would compute) and its cache slots and logits are copied to the G candidates
+            a_lo, a_hi = self.lo // G, self.hi // G
+            logits_u = st['logits_u'][a_lo:a_hi]
+            with torch.cuda.stream(self.stream):
+                self._launch_prefill(L0, st['tokens'][self.lo:self.hi:G, :L0], [t[:a_hi - a_lo] for t in self.kv], logits_u, None,
+                                     st['row_start_u'][a_lo:a_hi] if dec.row_prompts else None)
+                self._spread_to_candidates(L0, logits_u)
+        else:
+            self._launch_prefill(L0, self.tokens[:, :L0], self.kv, self.logits, self.live, self.row_start)
+        V = self.logits.shape[-1]
+        self._token_step(self.logits.data_ptr() + (L0 - 1) * V * 2, L0 * V, L0)
+        self._finish(None)
+
+    def _launch_prefill(self, L0, tokens, kv, logits, live, row_start) -> None:
+        dec, cap = self.dec, self.dec.decoder_config['num_text_ctx']
+        sess, pos = dec.decoder_session, dec.positional_embedding[0:L0]
+        if self.call.block:
+            sess.decoder_prefill(tokens, pos, self.cross, kv, cap, logits, self.sm, dec.sot_index, slot=self.slot, live_rows=live,
+                                 row_start=row_start)
+        else:
+            sess.decoder_step(tokens, pos, self.cross, None, cap, kv, cap, logits, 0, self.sm, slot=self.slot, live_rows=live,
+                              not_alone=self.call.not_alone, row_start=row_start)
+
+    def _spread_to_candidates(self, L0, logits_u) -> None:
+        """Shared cross K/V: the first L0 cache slots and the logits of every utterance's prefilled row, to its G candidates."""
+        n_u, G = logits_u.shape[0], self.dec._cross_group()
+        for t in self.kv:
+            first = t[:n_u, :, :, :L0].clone()
+            t.view(n_u, G, *t.shape[1:])[:, :, :, :, :L0] = first[:, None]
+        self.logits.view(n_u, G, L0, self.logits.shape[-1])[:] = logits_u[:, None]
+
+    def step(self, cur: int) -> None:
+        """One token step issued eagerly: token cur - 1 at the host's n_past = cur - 1."""
+        self._launch_step(self.tokens[:, cur - 1:cur], self.dec.positional_embedding[cur - 1:cur], cur - 1)
+        self._token_step(self.logits.data_ptr(), self.logits.shape[-1], cur)
+        self._finish(None)
+
+    def step_counted(self, counter: Tensor) -> None:
+        """The token step in the form that is captured: the whole token buffer, n_past read from the device counter, which the
+        step's finish advances -- the call is the same for every token."""
+        self._launch_step(self.tokens, self.dec.positional_embedding, 1, n_past_dev=counter, n_new=1)
+        self._token_step(self.logits.data_ptr(), self.logits.shape[-1], 0, n_past_dev=counter)
+        self._finish(counter)
+
+    def _launch_step(self, tokens, pos, n_past, **counted) -> None:
+        cap = self.dec.decoder_config['num_text_ctx']
+        self.dec.decoder_session.decoder_step(tokens, pos, self.cross, self.kv, cap, self.kv, cap, self.logits, n_past, self.sm,
+                                              slot=self.slot, live_rows=self.live, not_alone=self.call.not_alone,
+                                              row_start=self.row_start, cross_group=self.dec._cross_group(),
+                                              live_groups=self.live_groups, **counted)
+
+    def _token_step(self, logits_ptr, row_stride, cur_len, n_past_dev=None) -> None:
+        """What follows a group's decoder launch: the fused greedy step, or the beam step and the cache reorder."""
+        dec, call = self.dec, self.call
+        if call.beam:
+            dec._beam(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, self.kv_table, call.ignore_eot, n_past_dev=n_past_dev)
+        else:
+            dec._greedy(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, n_past_dev=n_past_dev, temperature=call.temperature)
+
+    def _finish(self, counter: Optional[Tensor]) -> None:
+        """End of a group's step: advance its device step counter (graph replay) and, with per-row completion, rebuild its list of
+        live rows from the flags the token step has just updated."""
+        lib, n = native.load_library(), self.hi - self.lo
+        counter_ptr = counter.data_ptr() if counter is not None else None
+        if self.live is not None and self.live_groups is not None:
+            native.check(lib.wm_step_finish_group(counter_ptr, self.done.data_ptr(), n, self.dec._cross_group(), self.live.data_ptr(),
+                                                  self.live_groups.data_ptr(), self.sm), "wm_step_finish_group")
+        elif self.live is not None:
+            native.check(lib.wm_step_finish(counter_ptr, self.done.data_ptr(), n, self.live.data_ptr(), self.sm), "wm_step_finish")
+        elif counter is not None:
+            native.check(lib.wm_step_advance(counter_ptr, self.sm), "wm_step_advance")
+
+
 class WhisperDecoding:
     def __init__(self, engine_dir, only_torch: bool = False, vocab_path: Optional[str] = None,
                  options: Optional[DecodingOptions] = None, row_prompts: bool = False, shared_cross_kv: bool = False,
@@ -775,40 +947,30 @@ class WhisperDecoding:
         n_audio, dev = audio_features.shape[0], audio_features.device
         cfg = self.decoder_config
         st = self._fast_state(n_audio * self._cross_group(), dev)     # (shared cross K/V: the candidates' buffer set, its first n_audio rows)
-        n_micro_, bounds_ = self._groups(n_audio, unit=1)   # groups of up to eight rows stepped one at a time may run as ONE launch per step
-        one_row = (n_micro_ == 1 or self.lang_id_sequential) and not self.force_not_alone and any(hi - lo <= 8 for lo, hi in bounds_)
-        if one_row and native.chain_status()["error_pending"]:                  # (a peek at a host word: no synchronisation)
-            self._chain_gave_up("found before the language pass", foreign=True)  # somebody else's give-up: said loudly, acknowledged, not ours to repeat
+        n_micro, bounds = self._groups(n_audio, unit=1)
+        one_row = self._may_run_alone(bounds, n_micro, self.lang_id_sequential, "found before the language pass")
         cross = self._cross_persistent(audio_features, st)
         if 'lang_logits' not in st:
             st['lang_logits'] = torch.empty((n_audio, 1, cfg['vocab_size']), dtype=torch.float16, device=dev)
             st['sot'] = torch.full((n_audio, 1), self.tokenizer.sot, dtype=torch.int32, device=dev)
-        n_micro, bounds = self._groups(n_audio, unit=1)
         main = torch.cuda.current_stream()
         streams = self._group_streams(n_micro, dev)
         cap = cfg['num_text_ctx']
         use_graph = self.use_graphs and self.graph_prefill and self.decoder_session.qkv_amax is None and not self.profile_eager_passes
+        na = steps_side_by_side(n_micro, self.lang_id_sequential, self.force_not_alone)
         for g, (lo, hi) in enumerate(bounds):
-            streams[g].wait_stream(main)
+            fork(main, streams[g:g + 1])
             if self.lang_id_sequential and g > 0:
                 streams[g].wait_stream(streams[g - 1])     # one group at a time: kernels are timed un-shared (bench.py)
-            na = (n_micro > 1 and not self.lang_id_sequential) or self.force_not_alone
 
-            def issue_lang(g=g, lo=lo, hi=hi, na=na):
+            def issue_lang(g=g, lo=lo, hi=hi):
                 self.decoder_session.decoder_step(st['sot'][lo:hi], self.positional_embedding[0:1],
                                                   [t[lo:hi] for t in cross], None, cap, [t[lo:hi] for t in st['kv']], cap,
                                                   st['lang_logits'][lo:hi], 0, streams[g].cuda_stream, slot=g, not_alone=na)
             # a launch per kernel (more than eight rows, or groups side by side): ~ 290 eager launches per group -> a replayed graph from the
             # second batch on.  (Up to eight rows alone the pass is the one-launch step: four launches, nothing to replay.)
-            lkey = (n_micro, g, 'lang', na)
-            if use_graph and (na or hi - lo > 8) and lkey in st['graphs']:
-                with torch.cuda.stream(streams[g]):
-                    st['graphs'][lkey].replay()
-            else:
-                issue_lang()
-                if use_graph and (na or hi - lo > 8):
-                    self._capture(st, lkey, streams[g], issue_lang)
-            main.wait_stream(streams[g])
+            self._replay_or_issue(st, language_key(n_micro, g, na), streams[g], issue_lang, use_graph and (na or hi - lo > 8))
+            join(main, streams[g:g + 1])
         language_tokens, language_probs, languages = self._language_from_logits(
             st['lang_logits'][:, 0].float(), n_audio, single)                # (brings the logits to the host: the pass has finished)
         if one_row and not _retry and self._chain_gave_up("language pass"):
@@ -1031,7 +1193,7 @@ class WhisperDecoding:
         )
         if self._cross_group() > 1:
             # shared cross K/V: the prefill runs on ONE row per utterance (the candidates begin alike); its logits, and the first slot of
-            # every utterance, before they are copied to the candidates' rows (_main_loop)
+            # every utterance, before they are copied to the candidates' rows (_Group.prefill)
             n_utt = n_batch // self._cross_group()
             st.update(logits_u=torch.empty((n_utt, self.initial_token_length, V), dtype=torch.float16, device=device),
                       row_start_u=torch.zeros(n_utt, dtype=torch.int32, device=device) if self.row_prompts else None)
@@ -1155,12 +1317,39 @@ class WhisperDecoding:
 
     def _capture(self, st, key, stream, issue):
         """Capture what `issue()` enqueues on `stream` (it has just been issued eagerly once, so every buffer and every workspace state it
-        touches exists) into st['graphs'][key].  Thread-local error mode + CAPTURE_LOCK: see the token step's capture in main_loop."""
+        touches exists) into st['graphs'][key]."""
         stream.synchronize()
         graph = torch.cuda.CUDAGraph()
+        # capture_error_mode "thread_local" + CAPTURE_LOCK: the encoder of the NEXT batch may be in flight on a helper thread
+        # (WhisperEncoding.prefetch), which waits for events and issues launches on its own stream.  Under the default
+        # "global" mode such a call from ANY thread while this capture is open invalidates it (hipErrorStreamCaptureInvalidated
+        # -- seen once in ~ 25 bench runs: the window is three captures of a millisecond or two against one event wait per
+        # encoder layer); the lock keeps the helper out of the driver for the length of the capture as well.
+        # (torch.cuda.graph's __enter__ synchronises the DEVICE while the lock is held: during a group's first capture the
+        # helper cannot issue its next encoder layer until the layer in flight has finished -- 45-135 ms at B = 576, once
+        # per group and process; the group stream was synchronised just above, so nothing of this loop is waited for)
         with native.CAPTURE_LOCK, torch.cuda.graph(graph, stream=stream, capture_error_mode="thread_local"):
             issue()
         st['graphs'][key] = graph
+
+    def _replay_or_issue(self, st, key, stream, issue, use_graph) -> None:
+        """A pass whose call is the same every time, on `stream`: replayed from st['graphs'][key] where that exists, else issued -- and,
+        with `use_graph`, captured for the next time."""
+        if use_graph and key in st['graphs']:
+            with torch.cuda.stream(stream):
+                st['graphs'][key].replay()
+        else:
+            issue()
+            if use_graph:
+                self._capture(st, key, stream, issue)
+
+    def _may_run_alone(self, bounds, n_micro, sequential, where: str, peek: bool = True) -> bool:
+        """`groups_run_alone` for a pass about to be issued -- and, where it may, a look at the give-up word first: one found set now is
+        somebody else's (said loudly, acknowledged, not ours to repeat).  A peek at a host word: no synchronisation."""
+        alone = groups_run_alone(bounds, n_micro, sequential, self.force_not_alone)
+        if alone and peek and native.chain_status()["error_pending"]:
+            self._chain_gave_up(where, foreign=True)
+        return alone
 
     def _chain_gave_up(self, where: str, foreign: bool = False) -> bool:
         """Did a one-launch decode step (csrc/gemv_chain.hip: groups of up to eight rows) give up waiting for its workgroups since the last look?
@@ -1196,31 +1385,26 @@ class WhisperDecoding:
     def _live_list(self, st, n_micro, slot, lo, hi):
         """The group's list of rows still decoding (int32 [1 + n]: count, indices relative to the group), reset to
         "all of them"; wm_step_finish rebuilds it after every step from the `done` flags."""
-        key = (n_micro, slot)
-        if key not in st['live']:
-            st['live'][key] = torch.empty(1 + hi - lo, dtype=torch.int32, device=st['done'].device)
-        live = st['live'][key]
-        live[0] = hi - lo
-        live[1:] = torch.arange(hi - lo, dtype=torch.int32, device=live.device)
-        return live
+        return self._all_live(st, (n_micro, slot), hi - lo)
 
     def _live_groups(self, st, n_micro, slot, lo, hi):
         """... and, for candidates that share a cross K/V row, the group's list of utterances with a live row (int32 [1 + n / G]),
         reset likewise; wm_step_finish_group rebuilds both."""
-        G = self._cross_group()
-        key = (n_micro, slot, 'utterances')
-        n = (hi - lo) // G
+        return self._all_live(st, (n_micro, slot, 'utterances'), (hi - lo) // self._cross_group())
+
+    @staticmethod
+    def _all_live(st, key, n):
         if key not in st['live']:
             st['live'][key] = torch.empty(1 + n, dtype=torch.int32, device=st['done'].device)
-        lu = st['live'][key]
-        lu[0] = n
-        lu[1:] = torch.arange(n, dtype=torch.int32, device=lu.device)
-        return lu
+        live = st['live'][key]
+        live[0] = n
+        live[1:] = torch.arange(n, dtype=torch.int32, device=live.device)
+        return live
 
-    def _greedy(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None, temperature=None):
-        """Fused logit rules + arg-max + append for utterances [lo, hi) of the batch state `st`."""
+    def _fill_rules(self, io, st, lo, hi, logits_ptr, row_stride, cur_len, n_past_dev):
+        """The fields wm_greedy_io and wm_beam_io share: where rows [lo, hi) of the batch state `st` and their logits are, and the
+        logit rules."""
         tk = self.tokenizer
-        io = native.WmGreedyIO()
         io.logits, io.row_stride = logits_ptr, row_stride
         io.batch, io.n_vocab = hi - lo, self.decoder_config['vocab_size']
         io.tokens, io.tokens_ld, io.cur_len = st['tokens'][lo:hi].data_ptr(), st['tokens'].shape[1], cur_len
@@ -1232,10 +1416,14 @@ class WhisperDecoding:
         # 1: SuppressBlank + SuppressTokens + ApplyTimestampRules; 2: without_timestamps -- the reference then builds no timestamp
         # filter (W/decoding.py:337-346) and samples from the whole suppressed vocabulary
         io.apply_rules = 2 if self.options.without_timestamps else 1
-        io.n_done = st['n_done'].data_ptr()
         io.n_past_dev = n_past_dev.data_ptr() if n_past_dev is not None else None
-        io.done = st['done'][lo:hi].data_ptr()
+        io.done, io.n_done = st['done'][lo:hi].data_ptr(), st['n_done'].data_ptr()
         io.row_limit = st['row_limit'][lo:hi].data_ptr()
+
+    def _greedy(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None, temperature=None):
+        """Fused logit rules + arg-max + append for utterances [lo, hi) of the batch state `st`."""
+        io = native.WmGreedyIO()
+        self._fill_rules(io, st, lo, hi, logits_ptr, row_stride, cur_len, n_past_dev)
         # temperature > 0: the draw happens in the same kernel (Gumbel-max, counter-based generator keyed on the global row: lo + b);
         # the seed lives in device memory so that a replayed graph draws afresh in every main_loop call
         io.temperature = float(self.options.temperature if temperature is None else temperature)     # (a per-call temperature: main_loop)
@@ -1245,27 +1433,16 @@ class WhisperDecoding:
     def _beam(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, kv_table, ignore_eot, n_past_dev=None):
         """Beam step + cache reorder for rows [lo, hi) (whole utterances) of the batch state `st`: wm_beam_step applies the logit rules,
         picks and moves the beams, wm_kv_reorder lets every layer's self-attention cache rows follow their parents."""
-        tk, cfg, lib = self.tokenizer, self.decoder_config, native.load_library()
+        cfg, lib = self.decoder_config, native.load_library()
         K, MC = self.decoder.beam_size, self.decoder.max_candidates
         a_lo, a_hi = lo // K, hi // K
         io = native.WmBeamIO()
-        io.logits, io.row_stride = logits_ptr, row_stride
-        io.batch, io.n_vocab = hi - lo, cfg['vocab_size']
-        io.tokens, io.tokens_ld, io.cur_len = st['tokens'][lo:hi].data_ptr(), st['tokens'].shape[1], cur_len
-        io.sum_logprobs = st['sum_logprobs'][lo:hi].data_ptr()
-        io.suppress, io.n_suppress = st['suppress'].data_ptr(), st['n_suppress']
-        io.blank, io.n_blank = st['blank'].data_ptr(), st['n_blank']
-        io.sample_begin, io.eot, io.timestamp_begin = self.sample_begin, tk.eot, tk.timestamp_begin
-        io.max_initial_timestamp_index = -1 if self.max_initial_timestamp_index is None else self.max_initial_timestamp_index
-        io.apply_rules = 2 if self.options.without_timestamps else 1
+        self._fill_rules(io, st, lo, hi, logits_ptr, row_stride, cur_len, n_past_dev)
         io.beam_size, io.max_candidates, io.ignore_eot = K, MC, int(bool(ignore_eot))
-        io.n_past_dev = n_past_dev.data_ptr() if n_past_dev is not None else None
-        io.row_limit = st['row_limit'][lo:hi].data_ptr()
         io.parent = st['parent'][lo:hi].data_ptr()
         io.fin_tokens, io.fin_scores = st['fin_tokens'][a_lo:a_hi].data_ptr(), st['fin_scores'][a_lo:a_hi].data_ptr()
         io.fin_len, io.fin_count = st['fin_len'][a_lo:a_hi].data_ptr(), st['fin_count'][a_lo:a_hi].data_ptr()
         io.live_len = st['live_len'][a_lo:a_hi].data_ptr()
-        io.done, io.n_done = st['done'][lo:hi].data_ptr(), st['n_done'].data_ptr()
         ws = st['beam_ws'][lo * (K + 1) * 8: hi * (K + 1) * 8]
         io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
         native.check(lib.wm_beam_step(C.byref(io), stream), "wm_beam_step")
@@ -1299,19 +1476,13 @@ class WhisperDecoding:
         HBM-bound part of a step) the other group runs its latency-bound weight-streaming chain.
         Rows that have emitted EOT drop out of the attention kernels and a group whose rows are all
         finished is no longer stepped (`skip_finished_rows`): the loop's cost follows the live rows."""
+        # 1. option checks and mode selection
         features_in = audio_features
         temp = float(self.options.temperature if temperature is None else temperature)
         mode, n_cand = candidate_mode(self.options, self.fallback_best_of, temp)
         beam = self.beam and mode == "beam"                 # this call's decoder (fallback_best_of: samples above temperature 0)
         G = self._cross_group()
-        self._require_device_loop("main_loop")
-        if G > 1 and not audio_features.is_cuda:
-            raise ValueError("main_loop: shared_cross_kv needs the device loop (features on the GPU)")
-        if temp != self.options.temperature:
-            if (self.beam or self.n_group != 1) and self.fallback_best_of is None:
-                raise ValueError("a per-call temperature is not supported with beam_size / best_of: they decode at the instance's temperature")
-            if not self.device_sampling or not audio_features.is_cuda:
-                raise ValueError("a per-call temperature needs the device loop (device_sampling on, features on the GPU)")
+        self._check_device_call(audio_features, temp)
         if temp != 0 or self.n_group != 1 or self.beam:
             # Sampling options (W/decoding.py:274-300 temperature, :92-115 best_of + ranker).  Round 4: the device loop takes them --
             # the draw is a Gumbel-max inside the greedy kernel, candidates are rows like any others.  `device_sampling = False`
@@ -1320,20 +1491,73 @@ class WhisperDecoding:
                 return self.main_loop_reference(audio_features)
             if self.n_group > 1 and G == 1:      # candidates share their utterance's audio: the reference repeats the features too (:538-539 of this file)
                 audio_features = self._candidate_rows(audio_features)
-        dev = audio_features.device
-        tokens0 = self._initial_token_rows(audio_features.shape[0] * G // self.n_group, dev)
-        n_batch, L0 = tokens0.shape
-        assert n_batch == audio_features.shape[0] * G
-        cfg = self.decoder_config
-        V, cap = cfg['vocab_size'], cfg['num_text_ctx']
+        n_batch, dev = audio_features.shape[0] * G, audio_features.device
+        n_micro, bounds = self._groups(n_batch)
+        self._check_partition(n_micro)
+        # 2. state reset
+        tokens0 = self._initial_token_rows(n_batch // self.n_group, dev)
+        assert tokens0.shape[0] == n_batch
+        L0 = tokens0.shape[1]
         st = self._fast_state(n_batch, dev)
-        n_micro_, bounds_ = self._groups(n_batch)       # groups of up to eight rows stepped one at a time may run as ONE launch per token step
-        one_row = (n_micro_ == 1 or self.groups_sequential) and not self.force_not_alone and any(hi - lo <= 8 for lo, hi in bounds_)
-        if one_row and not _retry and native.chain_status()["error_pending"]:   # (a peek at a host word: no synchronisation)
-            self._chain_gave_up("found before the decode loop", foreign=True)   # somebody else's give-up: said loudly, acknowledged, not ours to repeat
-        if temp != 0:     # a fresh seed per call from torch's generator: torch.manual_seed makes a run repeatable
-            if not _retry:
-                st['seed'].copy_(torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32))
+        one_row = self._may_run_alone(bounds, n_micro, self.groups_sequential, "found before the decode loop", peek=not _retry)
+        cross = self._reset_state(st, audio_features, tokens0, row_limit, n_cand, reseed=temp != 0 and not _retry)
+        if self.cu_partition and n_micro > 1 and self.decoder_session.qkv_amax is None and row_limit is None and temp == self.options.temperature:
+            return self._main_loop_partitioned(audio_features, st, cross, L0, n_micro, bounds, ignore_eot)
+        # 3. group construction
+        use_graph = self.use_graphs and self.decoder_session.qkv_amax is None
+        block = self.block_prefill and L0 > 4
+        call = _Call(st=st, cross=cross, L0=L0, n_micro=n_micro, beam=beam, ignore_eot=ignore_eot, temperature=temp,
+                     use_live=bool(self.skip_finished_rows) and not ignore_eot and max(hi - lo for lo, hi in bounds) <= 1024,
+                     not_alone=steps_side_by_side(n_micro, self.groups_sequential, self.force_not_alone),
+                     bkey=call_key(beam, ignore_eot, G, temp, self.options.temperature),
+                     use_graph=use_graph, block=block, graph_prefill=use_graph and self.graph_prefill and (L0 <= 4 or block))
+        main = torch.cuda.current_stream()
+        streams = self._group_streams(n_micro, dev)
+        groups = [_Group(self, call, g, lo, hi, streams[g]) for g, (lo, hi) in enumerate(bounds)]
+        fork(main, streams)
+        # 4. the loop
+        cur, nsp_dev = self._run_groups(call, groups, main, streams)
+        # 5. finish
+        join(main, streams)
+        finish = self._finish_beam_loop if beam else self._finish_main_loop
+        out = finish(st, cur, L0, n_batch, ignore_eot, nsp_dev)
+        self._rep_cache = None        # the candidates' repeated features (best_of): the language pass and this loop have both used them
+        # 6. the give-up retry
+        if one_row and not _retry and self._chain_gave_up("decode loop"):
+            # one-row groups run the token step as ONE launch whose workgroups wait for each other with bounded spins; a wait that was
+            # given up invalidates the step and every token after it.  The utterance is decoded again, in this process, on the
+            # launch-per-kernel path (the library has taken the device off the one-launch forms; the captured graphs are gone).
+            return self.main_loop(features_in, ignore_eot=ignore_eot, row_limit=row_limit, _retry=True, temperature=temperature)
+        return out
+
+    def _check_device_call(self, audio_features, temp: float) -> None:
+        """What a main_loop call at temperature `temp` over `audio_features` refuses before it touches anything."""
+        self._require_device_loop("main_loop")
+        if self._cross_group() > 1 and not audio_features.is_cuda:
+            raise ValueError("main_loop: shared_cross_kv needs the device loop (features on the GPU)")
+        if temp != self.options.temperature:
+            if (self.beam or self.n_group != 1) and self.fallback_best_of is None:
+                raise ValueError("a per-call temperature is not supported with beam_size / best_of: they decode at the instance's temperature")
+            if not self.device_sampling or not audio_features.is_cuda:
+                raise ValueError("a per-call temperature needs the device loop (device_sampling on, features on the GPU)")
+
+    def _check_partition(self, n_micro: int) -> None:
+        """What the CU-partitioned schedule does not serve."""
+        if not self.cu_partition:
+            return
+        if n_micro > 1 and self.beam:
+            raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
+        if self.block_prefill:
+            raise ValueError("block_prefill is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
+        if n_micro > 1 and self.row_prompts:
+            raise ValueError("row_prompts is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
+
+    def _reset_state(self, st, audio_features, tokens0, row_limit, n_cand: int, reseed: bool):
+        """The batch state `st` as a device-loop call finds it: seed, tokens, flags, per-row limits and first slots.  Returns the cross
+        K/V of `audio_features` in the state's persistent buffers."""
+        n_batch, L0 = tokens0.shape
+        if reseed:        # a fresh seed per call from torch's generator: torch.manual_seed makes a run repeatable
+            st['seed'].copy_(torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32))
         cross = self._cross_persistent(audio_features, st)
         st['tokens'].zero_()
         st['tokens'][:, :L0] = tokens0.to(torch.int32)
@@ -1344,7 +1568,7 @@ class WhisperDecoding:
             st['fin_count'].zero_()
             st['live_len'].zero_()
         if row_limit is not None:
-            row_limit = torch.as_tensor(row_limit).to(device=dev, dtype=torch.int32)
+            row_limit = torch.as_tensor(row_limit).to(device=tokens0.device, dtype=torch.int32)
             assert row_limit.shape == (n_batch,)
             st['row_limit'].copy_(row_limit)
         else:
@@ -1353,203 +1577,81 @@ class WhisperDecoding:
             # a sampling call of a beam instance: candidates j >= n_cand of every utterance are closed before their first token (EOT,
             # nothing booked): they drop out of the kernels with the first live list and never reach the ranker (post_process)
             st['row_limit'].view(-1, self.n_group)[:, n_cand:] = 0
-        n_micro, bounds = self._groups(n_batch)
-        if self.cu_partition and n_micro > 1 and self.beam:
-            raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
-        if self.cu_partition and self.block_prefill:
-            raise ValueError("block_prefill is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
-        if self.cu_partition and n_micro > 1 and self.row_prompts:
-            raise ValueError("row_prompts is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
         if self.row_prompts:
             st['row_start'].copy_(self._row_starts)
-            if G > 1:
-                st['row_start_u'].copy_(self._row_starts[::G])
-        if self.cu_partition and n_micro > 1 and self.decoder_session.qkv_amax is None and row_limit is None and temp == self.options.temperature:
-            return self._main_loop_partitioned(audio_features, st, cross, L0, n_micro, bounds, ignore_eot)
-        use_live = bool(self.skip_finished_rows) and not ignore_eot and max(hi - lo for lo, hi in bounds) <= 1024
-        main = torch.cuda.current_stream()
-        streams = self._group_streams(n_micro, dev)
-        sess, pos = self.decoder_session, self.positional_embedding
-        groups = []
-        for g, (lo, hi) in enumerate(bounds):
-            groups.append(dict(lo=lo, hi=hi, stream=streams[g].cuda_stream, slot=g, active=True,
-                               kv=[t[lo:hi] for t in st['kv']], cross=[t[lo // G:hi // G] for t in cross],
-                               live_groups=self._live_groups(st, n_micro, g, lo, hi) if use_live and G > 1 else None,
-                               logits=st['logits'][lo:hi], tokens=st['tokens'][lo:hi], done=st['done'][lo:hi],
-                               live=self._live_list(st, n_micro, g, lo, hi) if use_live else None,
-                               row_start=st['row_start'][lo:hi] if self.row_prompts else None))
-            if self.beam:       # the group's cache rows per layer as a device-resident pointer table (wm_kv_reorder; stable like the buffers)
-                if (n_micro, g) not in st['kv_tables']:
-                    st['kv_tables'][(n_micro, g)] = torch.tensor([t.data_ptr() for t in groups[-1]['kv']], dtype=torch.int64, device=dev)
-                groups[-1]['kv_table'] = st['kv_tables'][(n_micro, g)]
-        for s_ in streams:
-            s_.wait_stream(main)
-        cur = L0
-        steps_done = 0
-        lib = native.load_library()
-        use_graph = self.use_graphs and self.decoder_session.qkv_amax is None
-        # stream-parallel groups: the steps of two groups are in flight at once, so none of them may take a one-launch form (two 256-workgroup
-        # launches side by side can each hold half of the chip and wait for the other half: ADVICE r5, whisper_mi355.h `not_alone`)
-        shared = (n_micro > 1 and not self.groups_sequential) or self.force_not_alone
+            if self._cross_group() > 1:
+                st['row_start_u'].copy_(self._row_starts[::self._cross_group()])
+        return cross
 
-        def finish_step(gr, counter):
-            # end of a group's step: advance its device step counter (graph replay) and, with per-row completion,
-            # rebuild its list of live rows from the flags the greedy kernel has just updated
-            if gr['live'] is not None and gr['live_groups'] is not None:
-                native.check(lib.wm_step_finish_group(counter.data_ptr() if counter is not None else None, gr['done'].data_ptr(), gr['hi'] - gr['lo'], G,
-                                                      gr['live'].data_ptr(), gr['live_groups'].data_ptr(), gr['stream']), "wm_step_finish_group")
-            elif gr['live'] is not None:
-                native.check(lib.wm_step_finish(counter.data_ptr() if counter is not None else None, gr['done'].data_ptr(),
-                                                gr['hi'] - gr['lo'], gr['live'].data_ptr(), gr['stream']), "wm_step_finish")
-            elif counter is not None:
-                native.check(lib.wm_step_advance(counter.data_ptr(), gr['stream']), "wm_step_advance")
+    def _issue_step(self, call: _Call, gr: _Group, i: int, cur: int) -> None:
+        """Step `i` of one group, on its stream: replayed where a graph of it exists, else issued (and captured for the next time)."""
+        st, graphs = call.st, call.st['graphs']
+        if i == 0:
+            # the prefill (L0 tokens on an empty cache) + the first token step.  Round 6: replayed from a graph from the second
+            # batch on -- the call is the same for every batch (state buffers, L0 and the start position are fixed), and issued
+            # eagerly its ~ 390 launches per group are HOST-bound at small and middle batches (7 us each: 2.7 ms per group where the
+            # GPU needs 1.7 at one utterance; with the language pass 9.5 ms per batch of 2 x 8)
+            self._replay_or_issue(st, gr.prefill_key, gr.stream, lambda: gr.prefill(call.L0), call.graph_prefill)
+        elif call.use_graph and gr.step_key in graphs:
+            if i == 1 or st['counters'][gr.fresh_key]:
+                # the device step counter holds n_past = cur - 1; (re)seed it on the group's stream
+                with torch.cuda.stream(gr.stream):
+                    st['counters'][gr.step_key].fill_(cur - 1)
+                st['counters'][gr.fresh_key] = False
+            with torch.cuda.stream(gr.stream):
+                graphs[gr.step_key].replay()
+        else:
+            gr.step(cur)
+            if call.use_graph:
+                # capture ONE decode step (decoder + token step + counter advance) of this group;
+                # every later token replays it: T is read from a device counter inside the kernels
+                counter = torch.zeros(1, dtype=torch.int32, device=gr.done.device)
+                self._capture(st, gr.step_key, gr.stream, lambda: gr.step_counted(counter))
+                st['counters'][gr.step_key] = counter
+                st['counters'][gr.fresh_key] = True
 
-        def token_step(gr, logits_ptr, row_stride, cur_len, sm, n_past_dev=None):
-            # what follows a group's decoder launch: the fused greedy step, or the beam step and the cache reorder
-            if beam:
-                self._beam(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, gr['kv_table'], ignore_eot, n_past_dev=n_past_dev)
-            else:
-                self._greedy(st, gr['lo'], gr['hi'], logits_ptr, row_stride, cur_len, sm, n_past_dev=n_past_dev, temperature=temp)
-
-        bkey = ('beam', bool(ignore_eot)) if beam else ()         # (ignore_eot is an argument of the captured beam step)
-        if G > 1:
-            bkey += (('cross_group', G),)
-        if temp != self.options.temperature:
-            bkey += (('temperature', temp),)                           # (so is the temperature: a per-call one has graphs of its own)
-        last_issued = None
+    def _run_groups(self, call: _Call, groups: List[_Group], main, streams):
+        """The loop itself: per token every active group's step, and the three points of it where the host looks.  Returns the length
+        the rows have reached and the no-speech probabilities (on the device, or None)."""
+        st, cap = call.st, self.decoder_config['num_text_ctx']
+        cur, steps_done, nsp_dev, last_issued = call.L0, 0, None, None
         for i in range(self.sample_len):
             for gr in groups:
-                if not gr['active']:
+                if not gr.active:
                     continue
-                lo, hi, sm, slot = gr['lo'], gr['hi'], gr['stream'], gr['slot']
-                if self.groups_sequential and n_micro > 1:
+                if self.groups_sequential and call.n_micro > 1:
                     if last_issued is not None:
-                        streams[slot].wait_stream(streams[last_issued])
-                    last_issued = slot
-                gkey = (n_micro, slot, use_live) + bkey
-                if i == 0:
-                    # the prefill (L0 tokens on an empty cache) + the first greedy step.  Round 6: replayed from a graph from the second
-                    # batch on -- the call is the same for every batch (state buffers, L0 and the start position are fixed), and issued
-                    # eagerly its ~ 390 launches per group are HOST-bound at small and middle batches (7 us each: 2.7 ms per group where the
-                    # GPU needs 1.7 at one utterance; with the language pass 9.5 ms per batch of 2 x 8)
-                    pkey = (n_micro, slot, use_live, 'prefill', L0, shared) + bkey
-
-                    block = self.block_prefill and L0 > 4       # one pass over the whole start block (wm_decoder_prefill), logits from sot_index on
-
-                    def issue_prefill(gr=gr, lo=lo, hi=hi, sm=sm, slot=slot, block=block):
-                        if G > 1:
-                            # shared cross K/V: the candidates of an utterance begin with the same tokens over the same audio, so ONE row
-                            # per utterance is prefilled (group 1, on the utterances' cross K/V and the group's first cache rows: what
-                            # each candidate's row would compute) and its cache slots and logits are copied to the G candidates
-                            a_lo, a_hi = lo // G, hi // G
-                            n_u = a_hi - a_lo
-                            with torch.cuda.stream(streams[slot]):
-                                if block:
-                                    sess.decoder_prefill(st['tokens'][lo:hi:G, :L0], pos[0:L0], gr['cross'], [t[:n_u] for t in gr['kv']], cap,
-                                                         st['logits_u'][a_lo:a_hi], sm, self.sot_index, slot=slot,
-                                                         row_start=st['row_start_u'][a_lo:a_hi] if self.row_prompts else None)
-                                else:
-                                    sess.decoder_step(st['tokens'][lo:hi:G, :L0], pos[0:L0], gr['cross'], None, cap, [t[:n_u] for t in gr['kv']], cap,
-                                                      st['logits_u'][a_lo:a_hi], 0, sm, slot=slot, not_alone=shared,
-                                                      row_start=st['row_start_u'][a_lo:a_hi] if self.row_prompts else None)
-                                for t in gr['kv']:
-                                    first = t[:n_u, :, :, :L0].clone()
-                                    t.view(n_u, G, *t.shape[1:])[:, :, :, :, :L0] = first[:, None]
-                                gr['logits'].view(n_u, G, L0, V)[:] = st['logits_u'][a_lo:a_hi, None]
-                        elif block:
-                            sess.decoder_prefill(gr['tokens'][:, :L0], pos[0:L0], gr['cross'], gr['kv'], cap, gr['logits'], sm, self.sot_index,
-                                                 slot=slot, live_rows=gr['live'], row_start=gr['row_start'])
-                        else:
-                            sess.decoder_step(gr['tokens'][:, :L0], pos[0:L0], gr['cross'], None, cap, gr['kv'], cap,
-                                              gr['logits'], 0, sm, slot=slot, live_rows=gr['live'], not_alone=shared, row_start=gr['row_start'])
-                        token_step(gr, gr['logits'].data_ptr() + (L0 - 1) * V * 2, L0 * V, L0, sm)
-                        finish_step(gr, None)
-                    if use_graph and self.graph_prefill and pkey in st['graphs']:
-                        with torch.cuda.stream(streams[slot]):
-                            st['graphs'][pkey].replay()
-                    else:
-                        issue_prefill()
-                        if use_graph and self.graph_prefill and (L0 <= 4 or block):        # (longer start sequences run as 4-token passes with copies between them: eager -- unless the block prefill takes them in one pass)
-                            self._capture(st, pkey, streams[slot], issue_prefill)
-                elif use_graph and gkey in st['graphs']:
-                    if i == 1 or st['counters'][gkey + ('fresh',)]:
-                        # the device step counter holds n_past = cur - 1; (re)seed it on the group's stream
-                        with torch.cuda.stream(streams[slot]):
-                            st['counters'][gkey].fill_(cur - 1)
-                        st['counters'][gkey + ('fresh',)] = False
-                    with torch.cuda.stream(streams[slot]):
-                        st['graphs'][gkey].replay()
-                else:
-                    sess.decoder_step(gr['tokens'][:, cur - 1:cur], pos[cur - 1:cur], gr['cross'], gr['kv'], cap,
-                                      gr['kv'], cap, gr['logits'], cur - 1, sm, slot=slot, live_rows=gr['live'], not_alone=shared,
-                                      row_start=gr['row_start'], cross_group=G, live_groups=gr['live_groups'])
-                    token_step(gr, gr['logits'].data_ptr(), V, cur, sm)
-                    finish_step(gr, None)
-                    if use_graph:
-                        # capture ONE decode step (decoder + fused greedy + counter advance) of this group;
-                        # every later token replays it: T is read from a device counter inside the kernels
-                        counter = torch.zeros(1, dtype=torch.int32, device=dev)
-                        streams[slot].synchronize()
-                        graph = torch.cuda.CUDAGraph()
-                        # capture_error_mode "thread_local" + CAPTURE_LOCK: the encoder of the NEXT batch may be in flight on a helper thread
-                        # (WhisperEncoding.prefetch), which waits for events and issues launches on its own stream.  Under the default
-                        # "global" mode such a call from ANY thread while this capture is open invalidates it (hipErrorStreamCaptureInvalidated
-                        # -- seen once in ~ 25 bench runs: the window is three captures of a millisecond or two against one event wait per
-                        # encoder layer); the lock keeps the helper out of the driver for the length of the capture as well.
-                        # (torch.cuda.graph's __enter__ synchronises the DEVICE while the lock is held: during a group's first capture the
-                        # helper cannot issue its next encoder layer until the layer in flight has finished -- 45-135 ms at B = 576, once
-                        # per group and process; the group stream was synchronised just above, so nothing of this loop is waited for)
-                        with native.CAPTURE_LOCK, torch.cuda.graph(graph, stream=streams[slot], capture_error_mode="thread_local"):
-                            sess.decoder_step(gr['tokens'], pos, gr['cross'], gr['kv'], cap, gr['kv'], cap,
-                                              gr['logits'], 1, sm, slot=slot, n_past_dev=counter, n_new=1, live_rows=gr['live'],
-                                              not_alone=shared, row_start=gr['row_start'], cross_group=G, live_groups=gr['live_groups'])
-                            token_step(gr, gr['logits'].data_ptr(), V, 0, sm, n_past_dev=counter)
-                            finish_step(gr, counter)
-                        st['graphs'][gkey], st['counters'][gkey] = graph, counter
-                        st['counters'][gkey + ('fresh',)] = True
+                        gr.stream.wait_stream(last_issued)
+                    last_issued = gr.stream
+                self._issue_step(call, gr, i, cur)
             if i == 0 and self.tokenizer.no_speech is not None:
-                # the greedy kernel has already written -inf into the LAST position's row only;
+                # the token step has already written -inf into the LAST position's row only;
                 # the <|sot|> position (no-speech probability, decoding.py:803-807) is untouched
-                for s_ in streams:
-                    main.wait_stream(s_)
+                join(main, streams)
                 probs_at_sot = st['logits'][:, self.sot_index].float().softmax(dim=-1)
                 nsp_dev = probs_at_sot[:, self.tokenizer.no_speech]
-                for s_ in streams:
-                    s_.wait_stream(main)
+                fork(main, streams)
             if i == 0 and self.first_token_event is not None:
                 # latency probe (bench.py): the first sampled token of every row exists once the groups' first steps have run
-                for s_ in streams:
-                    main.wait_stream(s_)
+                join(main, streams)
                 self.first_token_event.record(main)
-                for s_ in streams:
-                    s_.wait_stream(main)
+                fork(main, streams)
             cur += 1
             steps_done += 1
             if cur > cap:
                 break
-            if not ignore_eot and (steps_done % self.poll_every == 0):
+            if not call.ignore_eot and (steps_done % self.poll_every == 0):
                 # `done` is sticky (a finished row stays at EOT), so "every row is done" is monotone;
                 # poll it now and then instead of synchronising every step
-                for s_ in streams:
-                    main.wait_stream(s_)
+                join(main, streams)
                 done_host = st['done'].bool().cpu()
                 if bool(done_host.all()):
                     break
-                if use_live:
+                if call.use_live:
                     for gr in groups:         # a group with no live row left costs a whole chain of launches per token: drop it
-                        if gr['active'] and bool(done_host[gr['lo']:gr['hi']].all()):
-                            gr['active'] = False
-        for s_ in streams:
-            main.wait_stream(s_)
-        finish = self._finish_beam_loop if beam else self._finish_main_loop
-        out = finish(st, cur, L0, n_batch, ignore_eot, nsp_dev if self.tokenizer.no_speech is not None else None)
-        self._rep_cache = None        # the candidates' repeated features (best_of): the language pass and this loop have both used them
-        if one_row and not _retry and self._chain_gave_up("decode loop"):
-            # one-row groups run the token step as ONE launch whose workgroups wait for each other with bounded spins; a wait that was
-            # given up invalidates the step and every token after it.  The utterance is decoded again, in this process, on the
-            # launch-per-kernel path (the library has taken the device off the one-launch forms; the captured graphs are gone).
-            return self.main_loop(features_in, ignore_eot=ignore_eot, row_limit=row_limit, _retry=True, temperature=temperature)
-        return out
+                        if gr.active and bool(done_host[gr.lo:gr.hi].all()):
+                            gr.active = False
+        return cur, nsp_dev
 
     def _main_loop_partitioned(self, audio_features, st, cross, L0, n_micro, bounds, ignore_eot):
         """The decode loop scheduled for the chip (wm_decoder_step_multi): every group's cross-attention kernel
@@ -1563,10 +1665,9 @@ class WhisperDecoding:
         sess, pos, lib = self.decoder_session, self.positional_embedding, native.load_library()
         main = torch.cuda.current_stream()
         light, heavy = self._partition_streams(n_micro, dev)
-        for s_ in light + [heavy]:
-            s_.wait_stream(main)
+        fork(main, light + [heavy])
         light_ptrs, heavy_ptr = [s_.cuda_stream for s_ in light], heavy.cuda_stream
-        key = ('partition', n_micro)
+        key = partition_key(n_micro)
         if key not in st['graphs']:
             counters = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in bounds]
             views = [dict(kv=[t[lo:hi] for t in st['kv']], cross=[t[lo:hi] for t in cross], logits=st['logits'][lo:hi],
@@ -1589,11 +1690,9 @@ class WhisperDecoding:
                     self._greedy(st, lo, hi, plan['views'][g]['logits'].data_ptr() + (L0 - 1) * V * 2, L0 * V, cur, light_ptrs[g])
                 if self.tokenizer.no_speech is not None:
                     # the greedy kernel wrote -inf into the LAST position's row only; the <|sot|> row is untouched
-                    for s_ in light:
-                        main.wait_stream(s_)
+                    join(main, light)
                     nsp_dev = st['logits'][:, self.sot_index].float().softmax(dim=-1)[:, self.tokenizer.no_speech]
-                    for s_ in light:
-                        s_.wait_stream(main)
+                    fork(main, light)
             else:
                 if i == 1:
                     for g, s_ in enumerate(light):
@@ -1612,12 +1711,10 @@ class WhisperDecoding:
             if cur > cap:
                 break
             if not ignore_eot and (steps_done % self.poll_every == 0):
-                for s_ in light:
-                    main.wait_stream(s_)
+                join(main, light)
                 if bool((st['tokens'][:, cur - 1] == self.tokenizer.eot).all()):
                     break
-        for s_ in light + [heavy]:
-            main.wait_stream(s_)
+        join(main, light + [heavy])
         return self._finish_main_loop(st, cur, L0, n_batch, ignore_eot,
                                       nsp_dev if self.tokenizer.no_speech is not None else None)
 

@@ -211,7 +211,7 @@ class Session(object):
     def make_decoder_io(self, tokens: torch.Tensor, pos: torch.Tensor, cross: Sequence[torch.Tensor],
                         past: Optional[Sequence[torch.Tensor]], past_capacity: int,
                         present: Sequence[torch.Tensor], present_capacity: int, logits: torch.Tensor,
-                        n_past: int, qkv_amax: Optional[torch.Tensor] = None, slot: int = 0,
+                        n_past: int, *, qkv_amax: Optional[torch.Tensor] = None, slot: int = 0,
                         n_past_dev: Optional[torch.Tensor] = None, n_new: Optional[int] = None,
                         live_rows: Optional[torch.Tensor] = None, not_alone: bool = False,
                         row_start: Optional[torch.Tensor] = None, cross_group: int = 1,
@@ -283,14 +283,14 @@ class Session(object):
     def decoder_step(self, tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
                      stream: int, qkv_amax=None, slot: int = 0, n_past_dev=None, n_new=None, live_rows=None, not_alone: bool = False,
                      row_start=None, cross_group: int = 1, live_groups=None):
+        lead = (tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past)
+        kw = dict(qkv_amax=qkv_amax, slot=slot, n_past_dev=n_past_dev, n_new=n_new, live_rows=live_rows, not_alone=not_alone,
+                  row_start=row_start)
         if cross_group > 1:            # candidates that share their utterance's cross K/V
-            gio = self.make_decoder_group_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
-                                             qkv_amax, slot, n_past_dev, n_new, live_rows, not_alone, row_start,
-                                             cross_group=cross_group, live_groups=live_groups)
+            gio = self.make_decoder_group_io(*lead, cross_group=cross_group, live_groups=live_groups, **kw)
             check(self._engine.lib.wm_decoder_step_group(self._engine.handle, C.byref(gio), stream), "wm_decoder_step_group")
             return
-        io = self.make_decoder_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
-                                  qkv_amax, slot, n_past_dev, n_new, live_rows, not_alone, row_start)
+        io = self.make_decoder_io(*lead, **kw)
         check(self._engine.lib.wm_decoder_step(self._engine.handle, C.byref(io), stream), "wm_decoder_step")
 
     def decoder_prefill(self, tokens, pos, cross, present, capacity, logits, stream: int, logits_from: int, slot: int = 0,
@@ -298,8 +298,8 @@ class Session(object):
         """wm_decoder_prefill: the whole block tokens int32 [B, L] (L = 1 .. n_text_ctx) on the EMPTY cache `present` (appended in place,
         slots 0 .. L - 1) in one pass; logits fp16 [B, L, V] are written for the positions logits_from .. L - 1 only."""
         pio = native.WmPrefillIO()
-        pio.io = self.make_decoder_io(tokens, pos, cross, None, 0, present, capacity, logits, 0, None, slot, None, None, live_rows, False,
-                                      row_start, prefill=True)
+        pio.io = self.make_decoder_io(tokens, pos, cross, None, 0, present, capacity, logits, 0, slot=slot, live_rows=live_rows,
+                                      row_start=row_start, prefill=True)
         pio.logits_from = int(logits_from)
         pio._keep = pio.io
         check(self._engine.lib.wm_decoder_prefill(self._engine.handle, C.byref(pio), stream), "wm_decoder_prefill")
@@ -309,7 +309,7 @@ class Session(object):
         """wm_decoder_step_tap: the step on the launch-per-kernel path, with the cross-attention queries of `heads` (a ctypes
         int32 array of layer * n_head + head, ascending) written to rows n_past .. of q_tape fp16 [B, len(heads), capacity, 64]."""
         io = self.make_decoder_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
-                                  None, slot, None, None, None, True)
+                                  slot=slot, not_alone=True)
         assert q_tape.dtype == torch.float16 and q_tape.is_contiguous() and q_tape.shape[0] == tokens.shape[0] and q_tape.shape[1] == len(heads)
         tap = native.WmTapIO()
         tap.q_tape, tap.capacity = q_tape.data_ptr(), q_tape.shape[2]
