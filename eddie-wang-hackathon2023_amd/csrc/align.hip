@@ -13,6 +13,7 @@
 // No atomics, a fixed order of every sum: the result is deterministic.
 //   dtw_kernel        one workgroup per utterance walks the anti-diagonals (the last three in LDS, one barrier each, trace bytes in
 //                     the workspace), then walks back and writes the reversed path.
+#include "decode_math.h"
 #include "kernels.h"
 #include "../../include/whisper_mi355.h"
 
@@ -22,7 +23,6 @@
 namespace wm {
 namespace {
 
-constexpr float ALIGN_SCALE = 0.35355339059327373f;    // 64^-0.25 (attn_decode.hip: ATTN_SCALE)
 constexpr int A_OUT = 32;                              // frames a workgroup of align_matrix finishes
 constexpr int A_COLS = 48;                             // frames it computes: A_OUT + 2 * halo (halo <= 7) in three MFMA column blocks
 constexpr int A_ZS = 49;                               // LDS row stride of the tile (odd: a column walk is conflict-free)
@@ -32,7 +32,7 @@ constexpr int A_TAB = 32;                              // table entries per laun
 __device__ __forceinline__ half8v scale8(half8v x) {
     half8v y;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = (h16)mul_rn((float)x[e], ALIGN_SCALE);      // the product rounded to fp32, then to fp16
+    for (int e = 0; e < 8; ++e) y[e] = (h16)mul_rn((float)x[e], ATTN_SCALE);      // the product rounded to fp32, then to fp16
     return y;
 }
 

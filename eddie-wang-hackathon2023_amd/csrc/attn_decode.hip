@@ -5,9 +5,9 @@
 //   q, k are multiplied by d^-0.25 and rounded to fp16 (W/torch_model.py:93-95), scores are
 //   fp32 dot products rounded to fp16, softmax runs in fp32 over the whole key range
 //   (torch_model.py:100-101; attention.py:385-398), probabilities are rounded to fp16, P.V
-//   accumulates in fp32 and is rounded to fp16.  The self-attention's dot products and P.V sums are chains of fused
-//   multiply-adds (fmaf, written out: left to the compiler the same loop came out partly fused, partly not, differently in
-//   every copy of it -- and gemv_chain.hip runs a copy of the four-wave form that must agree with it bit for bit).
+//   accumulates in fp32 and is rounded to fp16.  The dot products and P.V sums are chains of fused multiply-adds (fmaf, written
+//   out: left to the compiler the same loop came out partly fused, partly not).  The expressions themselves live in decode_math.h,
+//   which the stages of the one-launch step (gemv_chain.hip) inline too.
 //   int8 KV: present = sat_s8(rne(x * (1/t))), past is used as fp16(q8) * t, the tokens of the
 //   current call are used un-quantised (attention.py:281-348; same contract as the MMHA kernel,
 //   decoderMaskedMultiheadAttentionTemplate.h:1501-1517, Utils.h:2276-2286,2357-2390).
@@ -38,12 +38,11 @@
 
 #include <atomic>
 
-#include "common.h"
+#include "decode_math.h"
 #include "kernels.h"
 
 namespace wm {
 
-constexpr float ATTN_SCALE = 0.35355339059327373f;    // 64^-0.25
 constexpr int MAX_L = 4;                              // query tokens per call handled per pass
 
 // ------------------------------------------------------------------------------------------------
@@ -131,9 +130,9 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
                 q += r0[0]; k += r0[C]; v += r0[2 * C];
             }
         }
-        q = r16(q + (p.bias ? (float)bq_raw : 0.f));
-        k = r16(k + (p.bias ? (float)bk_raw : 0.f));
-        v = r16(v + (p.bias ? (float)bv_raw : 0.f));
+        q = qkv_round(q, p.bias ? (float)bq_raw : 0.f);
+        k = qkv_round(k, p.bias ? (float)bk_raw : 0.f);
+        v = qkv_round(v, p.bias ? (float)bv_raw : 0.f);
         if (p.amax) {     // calibration hook: max |q|,|k|,|v| of this layer (smoothquant.py:117-175, F8)
             const float a = wave_max_nomfma(fmaxf(fabsf(q), fmaxf(fabsf(k), fabsf(v))));
             if (lane == 0) atomicMax((unsigned int*)p.amax, __float_as_uint(a));   // a >= 0: bit order = value order
@@ -144,14 +143,14 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
         const size_t off_k = (size_t)b * p.present_bstride + ((size_t)(0 * p.H + h) * p.present_cap + Tabs + i) * 64 + lane;
         const size_t off_v = (size_t)b * p.present_bstride + ((size_t)(1 * p.H + h) * p.present_cap + Tabs + i) * 64 + lane;
         if (I8) {
-            ((int8_t*)p.present)[off_k] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(k * inv_t)));
-            ((int8_t*)p.present)[off_v] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(v * inv_t)));
+            ((int8_t*)p.present)[off_k] = kv_cache_code(k, inv_t);
+            ((int8_t*)p.present)[off_v] = kv_cache_code(v, inv_t);
         } else {
             ((h16*)p.present)[off_k] = (h16)k;
             ((h16*)p.present)[off_v] = (h16)v;
         }
         // stash q rows in registers via LDS later; keep q of token i in s_q when processed
-        s_qall[i][lane] = (h16)r16(q * ATTN_SCALE);
+        s_qall[i][lane] = (h16)attn_scaled(q);
     }
     // copy-forward: when present is a different buffer than past (the reference's concat
     // semantics, attention.py:296-306), move the T cached rows of this head
@@ -196,24 +195,20 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnSelfParams p) {
 #pragma unroll
                             for (int e = 0; e < 16; ++e) {
                                 const int8_t q8 = (int8_t)((ws[e >> 2] >> (8 * (e & 3))) & 0xff);
-                                const float kd = r16(r16((float)q8 * t_dq) * ATTN_SCALE);
+                                const float kd = attn_scaled(r16((float)q8 * t_dq));
                                 acc = fmaf((float)s_q[c * 16 + e], kd, acc);
                             }
                         }
                     } else {
                         const half8v* kr = (const half8v*)(pastK + (size_t)j * 128);
 #pragma unroll
-                        for (int c = 0; c < 8; ++c) {
-                            const half8v w = j0 == 0 ? __builtin_bit_cast(half8v, kpre[c]) : kr[c];
-#pragma unroll
-                            for (int e = 0; e < 8; ++e)
-                                acc = fmaf((float)s_q[c * 8 + e], r16((float)w[e] * ATTN_SCALE), acc);
-                        }
+                        for (int c = 0; c < 8; ++c)
+                            acc = self_score_chunk8(s_q + c * 8, j0 == 0 ? __builtin_bit_cast(half8v, kpre[c]) : kr[c], acc);
                     }
                 } else {
                     const h16* kn = s_knew[j - T + i0];
 #pragma unroll 8
-                    for (int e = 0; e < 64; ++e) acc = fmaf((float)s_q[e], r16((float)kn[e] * ATTN_SCALE), acc);
+                    for (int e = 0; e < 64; ++e) acc = fmaf((float)s_q[e], attn_scaled((float)kn[e]), acc);
                 }
                 sc = r16(f32_as_is(acc));
             }
@@ -357,7 +352,7 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
     const float inv_t = 1.0f / p.kv_scale;
     if constexpr (I8) {                           // (256 threads: one code each, both tables; the barrier below covers it)
         const float d = r16((float)(int)(int8_t)(tid & 255) * t_dq);
-        s_lut[tid & 255] = r16(d * ATTN_SCALE);
+        s_lut[tid & 255] = attn_scaled(d);
         s_lut[256 + (tid & 255)] = d;
     }
     const size_t sstride = p.part_sstride ? (size_t)p.part_sstride : (size_t)p.B * p.L * p.ldp;
@@ -384,26 +379,26 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
                 const float* r0 = row + (size_t)s * sstride;
                 q += r0[0]; k += r0[C]; v += r0[2 * C];
             }
-            q = r16(q + (p.bias ? (float)bq_raw : 0.f));
-            k = r16(k + (p.bias ? (float)bk_raw : 0.f));
-            v = r16(v + (p.bias ? (float)bv_raw : 0.f));
+            q = qkv_round(q, p.bias ? (float)bq_raw : 0.f);
+            k = qkv_round(k, p.bias ? (float)bk_raw : 0.f);
+            v = qkv_round(v, p.bias ? (float)bv_raw : 0.f);
             if (p.amax) {     // calibration hook (see attn_self_kernel)
                 const float a = wave_max_nomfma(fmaxf(fabsf(q), fmaxf(fabsf(k), fabsf(v))));
                 if (lane == 0) atomicMax((unsigned int*)p.amax, __float_as_uint(a));
             }
             s_knew[i][lane] = (h16)k;
             s_vnew[i][lane] = (h16)v;
-            if constexpr (I8) s_lut[512 + i * 64 + lane] = r16(k * ATTN_SCALE);      // (k is an fp16 value already)
+            if constexpr (I8) s_lut[512 + i * 64 + lane] = attn_scaled(k);
             const size_t off_k = (size_t)b * p.present_bstride + ((size_t)(0 * p.H + h) * p.present_cap + Tabs + i) * 64 + lane;
             const size_t off_v = (size_t)b * p.present_bstride + ((size_t)(1 * p.H + h) * p.present_cap + Tabs + i) * 64 + lane;
             if (I8) {
-                ((int8_t*)p.present)[off_k] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(k * inv_t)));
-                ((int8_t*)p.present)[off_v] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(v * inv_t)));
+                ((int8_t*)p.present)[off_k] = kv_cache_code(k, inv_t);
+                ((int8_t*)p.present)[off_v] = kv_cache_code(v, inv_t);
             } else {
                 ((h16*)p.present)[off_k] = (h16)k;
                 ((h16*)p.present)[off_v] = (h16)v;
             }
-            s_qall[i][lane] = (h16)r16(q * ATTN_SCALE);
+            s_qall[i][lane] = (h16)attn_scaled(q);
         }
     }
     // copy-forward when present is a different buffer than past (the reference's concat semantics, attention.py:296-306)
@@ -451,13 +446,8 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
                             acc = fmaf((float)s_q[c * 16 + e], s_lut[idx], acc);      // r16(r16((float)code * t_dq) * ATTN_SCALE) | r16(k_new * ATTN_SCALE)
                         }
                     } else {
-                        const half8v wh = __builtin_bit_cast(half8v, w);
                         const half8v kn8 = *(const half8v*)(&s_knew[jn][c * 8]);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float xk = cached ? (float)wh[e] : (float)kn8[e];
-                            acc = fmaf((float)s_q[c * 8 + e], r16(xk * ATTN_SCALE), acc);
-                        }
+                        acc = self_score_chunk8(s_q + c * 8, cached ? __builtin_bit_cast(half8v, w) : kn8, acc);
                     }
                 }
                 sc = r16(f32_as_is(acc));
@@ -492,9 +482,7 @@ __global__ __launch_bounds__(64 * SELF_WAVES) void attn_self_wg_kernel(AttnSelfP
                 for (int d = 0; d < 16; ++d)
                     o[d] = fmaf(pj, s_lut[256 + ((ws[d >> 2] >> (8 * (d & 3))) & 0xff)], o[d]);      // = r16((float)code * t_dq)
             } else {
-                const half8v wh = __builtin_bit_cast(half8v, w);
-#pragma unroll
-                for (int d = 0; d < 8; ++d) o[d] = fmaf(pj, (float)wh[d], o[d]);
+                pv_row8(pj, __builtin_bit_cast(half8v, w), o);
             }
         };
 #pragma unroll
@@ -751,7 +739,7 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
             for (int q4 = 0; q4 < QV; ++q4) {
                 const float qs[4] = {qa[i][q4].x, qa[i][q4].y, qa[i][q4].z, qa[i][q4].w};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) qf[i][q4 * 4 + e] = r16(r16(qs[e] + bs[q4 * 4 + e]) * ATTN_SCALE);
+                for (int e = 0; e < 4; ++e) qf[i][q4 * 4 + e] = attn_scaled(qkv_round(qs[e], bs[q4 * 4 + e]));
             }
     }
 
@@ -763,7 +751,7 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
         for (int e = 0; e < DPL / 2; ++e) qh2[i][e] = half2v{(h16)qf[i][2 * e], (h16)qf[i][2 * e + 1]};
     const float k_scale = p.kv_q8_scale * ATTN_SCALE;
 
-    // the lane's DPL values of one K / V row as fp32 (fp16 storage, or the int8 codes themselves)
+    // int8 mode: the lane's 16 codes of one V row as fp32 (the fp16 rows go through decode_math.h as they are)
     auto unpack = [&](const u32x4& raw, float (&x)[DPL]) {
         if constexpr (I8) {
             const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
@@ -774,10 +762,6 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
                 x[4 * c + 0] = (float)lo[0]; x[4 * c + 1] = (float)lo[1];
                 x[4 * c + 2] = (float)hi[0]; x[4 * c + 3] = (float)hi[1];
             }
-        } else {
-            const half8v hv = __builtin_bit_cast(half8v, raw);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = (float)hv[e];
         }
     };
 
@@ -809,27 +793,23 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
                 }
             } else {
                 float ks[DPL];
-                unpack(cur[u], ks);
+                cross_scaled_key(__builtin_bit_cast(half8v, cur[u]), ks);
 #pragma unroll
-                for (int e = 0; e < DPL; ++e) ks[e] = r16(ks[e] * ATTN_SCALE);
-#pragma unroll
-                for (int i = 0; i < L; ++i) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int e = 0; e < DPL; ++e) acc = fmaf(qf[i][e], ks[e], acc);          // (written out: gemv_chain.hip runs a copy of this loop that must round the same way)
-                    accs[i] = acc;
-                }
+                for (int i = 0; i < L; ++i) accs[i] = cross_dot8(qf[i], ks);
             }
 #pragma unroll
             for (int i = 0; i < L; ++i) {
-                // sum over the LPR lanes that share a row: DPP moves inside the ALU (quad swaps, then the mirrored half-row brings
-                // the other quad's sum) instead of __shfl_xor, which compiles to ds_bpermute + a wait on the LDS counter per step --
-                // three dependent LDS round trips per row were most of this loop's issue time.  Same pairs, same sums.
-                float acc = accs[i];
-                acc += wave_dpp<0xB1>(acc);                       // lane ^ 1
-                acc += wave_dpp<0x4E>(acc);                       // lane ^ 2
-                if constexpr (LPR == 8) acc += wave_dpp<0x141>(acc);      // the other quad of the 8 (row_half_mirror)
-                const float sc = I8 ? r16(acc * k_scale) : r16(f32_as_is(acc));
+                // sum over the LPR lanes that share a row: DPP moves inside the ALU instead of __shfl_xor, which compiles to ds_bpermute +
+                // a wait on the LDS counter per step -- three dependent LDS round trips per row were most of this loop's issue time
+                float sc;
+                if constexpr (I8) {
+                    float acc = accs[i];
+                    acc += wave_dpp<0xB1>(acc);                       // lane ^ 1
+                    acc += wave_dpp<0x4E>(acc);                       // lane ^ 2
+                    sc = r16(acc * k_scale);
+                } else {
+                    sc = cross_row_score(accs[i]);
+                }
                 if (r < nkeys) {
                     if (sub == 0) s_sc[i][r] = sc;
                     mx[i] = fmaxf(mx[i], sc);
@@ -915,12 +895,16 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
             // no branch around the use of cur[u]: a path that skips it leaves its load pending at the loop head, and the
             // next prefetch into those registers would have to wait for it (rows past the end weigh 0; their data is the last row's)
             float vx[DPL];
-            unpack(cur[u], vx);
+            if constexpr (I8) unpack(cur[u], vx);
 #pragma unroll
             for (int i = 0; i < L; ++i) {
                 const float pr = r < nkeys ? s_sc[i][min(r, nkeys - 1)] : 0.f;
+                if constexpr (I8) {
 #pragma unroll
-                for (int e = 0; e < DPL; ++e) o[i][e] = fmaf(pr, vx[e], o[i][e]);
+                    for (int e = 0; e < DPL; ++e) o[i][e] = fmaf(pr, vx[e], o[i][e]);
+                } else {
+                    pv_row8(pr, __builtin_bit_cast(half8v, cur[u]), o[i]);
+                }
             }
         }
         // pin the accumulators here: pure arithmetic is free to sink below the NEXT prefetch otherwise, which turns the
@@ -936,17 +920,21 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
     static_assert(DPL % 8 == 0, "the cross-row steps take eight values at a time");
 #pragma unroll
     for (int i = 0; i < L; ++i) {
+        if constexpr (I8) {
 #pragma unroll
-        for (int e = 0; e < DPL; ++e) {
-            float v = o[i][e];
-            if constexpr (LPR == 4) v += __shfl_xor(v, 4);          // (int8 K/V only: no ALU-side exchange reaches lane ^ 4 exactly)
-            v += wave_dpp<0x128>(v);                                // lane ^ 8: row_ror:8 inside a row of 16 lanes
-            o[i][e] = v;
-        }
+            for (int e = 0; e < DPL; ++e) {
+                float v = o[i][e];
+                v += __shfl_xor(v, 4);                                  // (no ALU-side exchange reaches lane ^ 4 exactly)
+                v += wave_dpp<0x128>(v);                                // lane ^ 8: row_ror:8 inside a row of 16 lanes
+                o[i][e] = v;
+            }
 #pragma unroll
-        for (int e0 = 0; e0 < DPL; e0 += 8) {                       // lane ^ 16, lane ^ 32: permlane swaps, eight values per step (common.h:
-            wave_add_xor16_x8_nomfma(&o[i][e0]);                    // no LDS round trips; the same pairs and order as the __shfl_xor loop
-            wave_add_xor32_x8_nomfma(&o[i][e0]);                    // this replaces -- and as the single steps did until round 5)
+            for (int e0 = 0; e0 < DPL; e0 += 8) {                       // lane ^ 16, lane ^ 32: permlane swaps, eight values per step
+                wave_add_xor16_x8_nomfma(&o[i][e0]);
+                wave_add_xor32_x8_nomfma(&o[i][e0]);
+            }
+        } else {
+            cross_o_tail8(o[i]);                                        // lane ^ 8, ^ 16, ^ 32 inside the ALU: no LDS round trips
         }
     }
     if (rowi == 0) {
@@ -974,7 +962,8 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(AttnCrossParams p) {
 // combine the key-range splits: softmax-weighted merge of (max, sum, unnormalised o).  All of an item's partial results
 // are requested at once (lanes < nsplit: max and sum; every lane: its dim of each split's o), the factors travel by
 // shuffle -- one memory round trip instead of 3 x nsplit dependent ones (8 -> 2 us at batch 1, where this kernel runs
-// 32 times per token).  Sums are taken in split order, as before.
+// 32 times per token).  The per-piece step is merge_pieces4's (decode_math.h: merge_weight, products through mul_rn, sums in split
+// order); lane s holds piece s's factor, where the one-launch step's merge has every lane compute all four.
 __global__ __launch_bounds__(64) void attn_cross_combine_kernel(AttnCrossParams p) {
     const int h = blockIdx.x, i = blockIdx.z, d = threadIdx.x;
     int b = blockIdx.y;
@@ -990,14 +979,14 @@ __global__ __launch_bounds__(64) void attn_cross_combine_kernel(AttnCrossParams 
 #pragma unroll
     for (int s = 0; s < CROSS_MAX_SPLIT; ++s) ov[s] = w[min(s, p.nsplit - 1) * stride + 2 + d];
     const float m = wave_max_nomfma(ms);
-    const float f = d < p.nsplit ? __expf(ms - m) : 0.f;
-    const float lf = ls * f;
+    const float f = d < p.nsplit ? merge_weight(ms, m) : 0.f;
+    const float lf = mul_rn(ls, f);
     float den = 0.f, num = 0.f;
 #pragma unroll
     for (int s = 0; s < CROSS_MAX_SPLIT; ++s) {
         if (s < p.nsplit) {                       // wave-uniform
             den += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lf), s));     // (v_readlane: s is a constant after unrolling)
-            num += mul_rn(ov[s], __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f), s)));     // (product and sum rounded separately, as this loop always compiled: common.h)
+            num += mul_rn(ov[s], __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f), s)));
         }
     }
     p.out[(size_t)(b * p.L + i) * p.ldo + h * 64 + d] = (h16)(num / den);

@@ -34,7 +34,7 @@
 //    them: every cache row is written exactly once, slots >= L never.
 #include <type_traits>
 
-#include "common.h"
+#include "decode_math.h"
 #include "kernels.h"
 
 namespace wm {
@@ -44,7 +44,6 @@ namespace {
 constexpr int PF_KEYS = 64;
 constexpr int PF_AROW = 128;                       // LDS bytes per key row (64 halves, chunk-swizzled)
 constexpr int PF_TILE = PF_KEYS * PF_AROW;         // 8192
-constexpr float PF_SCALE = 0.35355339059327373f;   // 64^-0.25
 
 struct PrefillParams {
     const float* part; int ksplit; int ldp; size_t sstride; const h16* bias;   // self: q | k | v slabs, cross: q slabs
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(PrefillParams p) {
             float v[8];
             slab_row8(p.part + m * p.ldp + col, p.ksplit, p.sstride, p.bias ? p.bias + col : nullptr, v);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) qf[qb][s][j] = (h16)r16_f32(v[j] * PF_SCALE);
+            for (int j = 0; j < 8; ++j) qf[qb][s][j] = (h16)r16_f32(v[j] * ATTN_SCALE);
         }
     }
 
@@ -164,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(PrefillParams p) {
             half8v* ptr = (half8v*)(sK(buf) + (wid + 4 * i) * 1024 + lane * 16);
             half8v k = *ptr;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) k[j] = (h16)r16_f32((float)k[j] * PF_SCALE);
+            for (int j = 0; j < 8; ++j) k[j] = (h16)r16_f32((float)k[j] * ATTN_SCALE);
             *ptr = k;
         }
     };
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(PrefillParams p) {
             for (int i = 0; i < 2; ++i) {
                 half8v w;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) w[j] = kv == 0 ? (h16)r16_f32(x[i * 8 + j] * PF_SCALE) : (h16)x[i * 8 + j];
+                for (int j = 0; j < 8; ++j) w[j] = kv == 0 ? (h16)r16_f32(x[i * 8 + j] * ATTN_SCALE) : (h16)x[i * 8 + j];
                 *(half8v*)(dst + r * PF_AROW + (((2 * c4 + i) ^ ((r >> 1) & 7)) << 4)) = w;
             }
             if (append) {

@@ -63,8 +63,8 @@ const char* lab_env_str(const char* name);          // nullptr unless set and WM
 // the steps 32, 16, 8 a lane's value depends on lane mod 8 only, so the lane a rotation by 4 reaches holds exactly what lane ^ 4
 // holds; likewise for 2 and 1 with the quad permutations): results are bit-identical to the __shfl_xor form.
 // a * b rounded to fp32 ON ITS OWN: the statement keeps the compiler from fusing the product into a following addition (hipcc
-// contracts by default and decides per context -- two copies of one expression can round differently; the merges of the
-// cross-attention's key-range pieces exist in three places that must agree bit for bit)
+// contracts by default and decides per context: one expression inlined into two kernels can round differently -- as the merge of
+// the cross-attention's key-range pieces, decode_math.h, would)
 __device__ __forceinline__ float mul_rn(float a, float b) {
     float r = a * b;
     asm volatile("" : "+v"(r));

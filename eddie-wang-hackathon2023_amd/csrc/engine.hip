@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "decode_math.h"
 #include "engine_internal.h"
 
 namespace wm {
@@ -405,13 +406,12 @@ int wm_encoder_forward_range(const wm_engine* e, const void* mel, int B, void* o
             if (big(e->conv2, e, w.c1, 2 * C, M, w.x, C, e->gelu(), nullptr, 0, s, &p, cu_budget)) return 2;
         }
     }
-    const float qk_scale = 0.35355339059327373f;    // 64^-0.25
     for (int i = layer_begin; i < layer_end; ++i) {
         const EncLayer& L = e->enc[i];
         if (launch_layernorm(w.x, C, M, C, L.ln1g, L.ln1b, w.xn, C, s)) return 2;
         {
             GemmBigParams p{};
-            p.colscale_n = 2 * C; p.colscale = qk_scale;
+            p.colscale_n = 2 * C; p.colscale = ATTN_SCALE;
             if (big(L.qkv, e, w.xn, C, M, w.qkv, 3 * C, 0, nullptr, 0, s, &p, cu_budget, w.wq)) return 2;
         }
         AttnEncParams ap{w.qkv, 3 * C, B, T, H, w.ctx, C, 2 * cu_budget};      // two workgroups fill a CU's registers

@@ -44,7 +44,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "common.h"
+#include "decode_math.h"
 #include "epilogue.h"
 #include "kernels.h"
 
@@ -223,32 +223,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 5 : 4) void gemm_rows_kernel(Gem
             const u32x4 wv4 = wreg[i];
             if constexpr (REFILL) wreg[i] = wt[(size_t)min(t + RING, kt_total - 1) * 64];
             if (t < kt_total) {                               // wave-uniform
-                half8v b[NM];
-                if constexpr (WB == 16) {
-                    b[0] = __builtin_bit_cast(half8v, wv4);
-                } else if constexpr (WB == 8) {
-                    half2v h[8];
-                    cvt_s8x4_f16x4(wv4.x, h[0], h[1]);
-                    cvt_s8x4_f16x4(wv4.y, h[2], h[3]);
-                    cvt_s8x4_f16x4(wv4.z, h[4], h[5]);
-                    cvt_s8x4_f16x4(wv4.w, h[6], h[7]);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        b[0][2 * q] = h[q][0]; b[0][2 * q + 1] = h[q][1];
-                        b[1][2 * q] = h[4 + q][0]; b[1][2 * q + 1] = h[4 + q][1];
-                    }
-                } else {
-                    const uint32_t wv[4] = {wv4.x, wv4.y, wv4.z, wv4.w};
-                    const half2v bias8 = {(h16)1032.0f, (h16)1032.0f};
-#pragma unroll
-                    for (int m = 0; m < 4; ++m)
-#pragma unroll
-                        for (int sft = 0; sft < 4; ++sft) {
-                            const uint32_t bits = ((wv[m] >> (4 * sft)) & 0x000F000Fu) | 0x64006400u;   // fp16 (1024 + u) x 2
-                            const half2v pr = __builtin_bit_cast(half2v, bits) - bias8;                  // u - 8 = q, exact
-                            b[m][2 * sft] = pr[0]; b[m][2 * sft + 1] = pr[1];
-                        }
-                }
+                const WeightTile<WB> w = expand_weight_tile<WB>(wv4);
                 // this lane's KT / 4 inputs of the tile start at chunk t * (KT / 8) + g * NM
                 const int c0 = t * (KT / 8) + g * NM;
 #pragma unroll
@@ -258,7 +233,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 5 : 4) void gemm_rows_kernel(Gem
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt) {
                         const half8v a = *(const half8v*)(xrow + mt * 16 * row_bytes + off);
-                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b[m], acc[mt], 0, 0, 0);
+                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, w.b[m], acc[mt], 0, 0, 0);
                     }
                 }
             }

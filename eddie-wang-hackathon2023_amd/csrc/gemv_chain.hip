@@ -41,7 +41,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "decode_math.h"
 #include "kernels.h"
 
 namespace wm {
@@ -349,35 +349,10 @@ __device__ __forceinline__ void chain_stage(const GemvChainParams& p, const Chai
 #pragma unroll
         for (int i = 0; i < TB; ++i) {
             const bool valid = t_begin[j] + i < t_end[j];     // wave-uniform
-            half8v b[NM];
-            if constexpr (WB == 16) {
-                b[0] = __builtin_bit_cast(half8v, wreg[j][i]);
-            } else if constexpr (WB == 8) {
-                half2v h[8];
-                cvt_s8x4_f16x4(wreg[j][i].x, h[0], h[1]);
-                cvt_s8x4_f16x4(wreg[j][i].y, h[2], h[3]);
-                cvt_s8x4_f16x4(wreg[j][i].z, h[4], h[5]);
-                cvt_s8x4_f16x4(wreg[j][i].w, h[6], h[7]);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    b[0][2 * q] = h[q][0]; b[0][2 * q + 1] = h[q][1];
-                    b[1][2 * q] = h[4 + q][0]; b[1][2 * q + 1] = h[4 + q][1];
-                }
-            } else {
-                const uint32_t wv[4] = {wreg[j][i].x, wreg[j][i].y, wreg[j][i].z, wreg[j][i].w};
-                const half2v bias8 = {(h16)1032.0f, (h16)1032.0f};
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-#pragma unroll
-                    for (int sft = 0; sft < 4; ++sft) {
-                        const uint32_t bits = ((wv[m] >> (4 * sft)) & 0x000F000Fu) | 0x64006400u;
-                        const half2v pr = __builtin_bit_cast(half2v, bits) - bias8;
-                        b[m][2 * sft] = pr[0]; b[m][2 * sft + 1] = pr[1];
-                    }
-            }
+            const WeightTile<WB> w = expand_weight_tile<WB>(wreg[j][i]);
             if (valid) {
 #pragma unroll
-                for (int m = 0; m < NM; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[j][i][m], b[m], acc, 0, 0, 0);
+                for (int m = 0; m < NM; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[j][i][m], w.b[m], acc, 0, 0, 0);
             }
         }
         const int slice = wslot + 8 * j;
@@ -445,11 +420,9 @@ __device__ __forceinline__ void chain_stage(const GemvChainParams& p, const Chai
 }
 
 // ---- the cross-attention of the row as the chain's last stage --------------------------------------------------------------
-// attn_cross_kernel<1>'s arithmetic for ONE (head, key-range piece) per workgroup (attn_decode.hip: lane -> 8 dims of a key row,
-// 8 rows per wave instruction, wave w takes rows 32 w + 128 k ..., scores in LDS, maxima and sums met in wave order, P.V per lane
-// over its rows in sequence, the partial (max, sum, o[64]) left for the merge) -- bit for bit: the same expressions in the same
-// order, only the rows come from LDS, where waves 4-7 put them by DMA at the START of the launch (K and V do not depend on the
-// activations: their 96 KB fly while the chain's Linears run) instead of from memory through a register pipeline.
+// attn_cross_kernel<1>'s work for ONE (head, key-range piece) per workgroup, bit for bit: the same assignment of rows to lanes and
+// waves and the same arithmetic (decode_math.h).  Only the rows come from LDS, where waves 4-7 put them by DMA at the START of the
+// launch (K and V do not depend on the activations: their 96 KB fly while the chain's Linears run), not through a register pipeline.
 constexpr int CHAIN_CROSS_KEYS = 1536;
 constexpr size_t CHAIN_DYN_LDS = 100 * 1024;      // K and V rows of a piece (beside ~ 60 KB of static LDS, of 160)
 constexpr size_t CHAIN_DYN_LDS4 = 64 * 1024;      // 3 and 4 rows: the self-attention's cached rows only (beside ~ 85 KB of static LDS)
@@ -457,7 +430,6 @@ constexpr size_t CHAIN_DYN_LDS8 = 24 * 1024;      // 5 to 8 rows: the same besid
 constexpr int CHAIN_MAX_LAYERS = 32;               // layers of a whole-step launch (their descriptors and tables sit in LDS; Whisper large has 32)
 // what the attention stages take per LAYER (kernel arguments for a one-layer launch, the two tables in a whole-step launch)
 struct ChainLayerArgs { const h16* cross_kv; const h16* cross_qbias; void* self_cache; const h16* self_bias; float self_kv_scale; };
-constexpr float CHAIN_ATTN_SCALE = 0.35355339059327373f;    // 64^-0.25 (attn_decode.hip: ATTN_SCALE)
 constexpr unsigned CHAIN_EPOCH_LIVE = 0x80000000u;
 
 template <int NR>
@@ -537,16 +509,8 @@ __device__ __forceinline__ void chain_cross_stage(const GemvChainParams& p, cons
     float qf[DPL];
     float mx = -INFINITY;
     if (has_item && nkeys > 0) {
-        // q of this lane's 8 dims: one slab, bias, the two roundings (attn_cross_kernel's prologue at ksplit = 1)
 #pragma unroll
-        for (int e = 0; e < DPL; ++e) {
-            const float x = s_q[sub * DPL + e];
-            float qa = 0.f;
-            qa += x + 0.f;
-            qa += 0.f + 0.f;
-            const float bs = (float)qb8[e];
-            qf[e] = r16(r16(qa + bs) * CHAIN_ATTN_SCALE);
-        }
+        for (int e = 0; e < DPL; ++e) qf[e] = cross_q_one_slab(s_q[sub * DPL + e], qb8[e]);
         // ---- pass 1: scores -- a key's score is its own (no sum across keys), so ALL EIGHT waves take part: wave w scores the rows
         // attn_cross_kernel's wave w & 3 scores, in the iterations k with k & 1 == w >> 2 (the upper four waves have nothing else to
         // do once their K / V rows have landed).  The rows of two iterations are read from LDS before the first is used. ----------
@@ -569,15 +533,8 @@ __device__ __forceinline__ void chain_cross_stage(const GemvChainParams& p, cons
                 for (int u = 0; u < UNR; ++u) {
                     const int r = first + (k0 + 2 * kk) * STRIDE + u * RPI + rowi;
                     float ks[DPL];
-#pragma unroll
-                    for (int e = 0; e < DPL; ++e) ks[e] = r16((float)hv[kk][u][e] * CHAIN_ATTN_SCALE);
-                    float acc = 0.f;
-#pragma unroll
-                    for (int e = 0; e < DPL; ++e) acc = fmaf(qf[e], ks[e], acc);
-                    acc += wave_dpp<0xB1>(acc);
-                    acc += wave_dpp<0x4E>(acc);
-                    acc += wave_dpp<0x141>(acc);
-                    const float sc = r16(f32_as_is(acc));
+                    cross_scaled_key(hv[kk][u], ks);
+                    const float sc = cross_row_score(cross_dot8(qf, ks));
                     if (r < nkeys) {
                         if (sub == 0) s_sc[r] = sc;
                         mx = fmaxf(mx, sc);
@@ -624,18 +581,12 @@ __device__ __forceinline__ void chain_cross_stage(const GemvChainParams& p, cons
             for (int kk = 0; kk < KB; ++kk) {
                 if (k0 + kk >= nb) break;                                      // wave-uniform
 #pragma unroll
-                for (int u = 0; u < UNR; ++u) {
-#pragma unroll
-                    for (int e = 0; e < DPL; ++e) o[e] = fmaf(pr[kk][u], (float)hv[kk][u][e], o[e]);
-                }
+                for (int u = 0; u < UNR; ++u) pv_row8(pr[kk][u], hv[kk][u], o);
 #pragma unroll
                 for (int e = 0; e < DPL; ++e) asm volatile("" : "+v"(o[e]) : : "memory");
             }
         }
-#pragma unroll
-        for (int e = 0; e < DPL; ++e) o[e] += wave_dpp<0x128>(o[e]);
-        wave_add_xor16_x8_nomfma(o);                               // (attn_cross_kernel's steps, eight values at a time: no matrix instruction
-        wave_add_xor32_x8_nomfma(o);                               // of this wave is in flight here -- its last Linear stage ended microseconds ago)
+        cross_o_tail8(o);                                          // (this wave's last Linear stage, and its matrix instructions, ended microseconds ago)
         if (rowi == 0) {
 #pragma unroll
             for (int e = 0; e < DPL; ++e) s_o[wid][sub * DPL + e] = o[e];
@@ -654,8 +605,7 @@ __device__ __forceinline__ void chain_cross_stage(const GemvChainParams& p, cons
 // two items per workgroup (waves 0-3 | 4-7; the last ceil(items / 2) workgroups of the launch), and the rows come from memory into
 // REGISTERS: a wave's share of a piece is 12 K and 12 V loads of 16 bytes per lane, all 24 requested at the head of the stage -- the
 // workgroups that carry items idle through the two Linear stages in front of it (out, cq), so the rows fly while q is still being made.
-// The arithmetic is attn_cross_kernel's, bit for bit: wave w of the item scores rows 32 w + 128 k ..., maxima and sums met in wave order,
-// P.V per lane over its rows in sequence, (max, sum, o[64]) left for the merge as tagged granules.
+// Rows to lanes and waves as in attn_cross_kernel, arithmetic from decode_math.h; (max, sum, o[64]) left for the merge as tagged granules.
 __device__ __forceinline__ void chain_cross_stage4(const GemvChainParams& p, const ChainLayerArgs& la, unsigned epoch_q, int per_split,
                                                    float* s_sc_all /* [2][768] */, float (*s_redc)[2] /* [8] */, float (*s_o)[64] /* [8] */, float (*s_q)[64] /* [2] */, unsigned dead) {
     constexpr int DPL = 8, LPR = 8, RPI = 8, UNR = 4;
@@ -734,31 +684,16 @@ __device__ __forceinline__ void chain_cross_stage4(const GemvChainParams& p, con
     float mx = -INFINITY;
     if (worker) {
 #pragma unroll
-        for (int e = 0; e < DPL; ++e) {
-            const float x = s_q[half][sub * DPL + e];
-            float qa = 0.f;
-            qa += x + 0.f;
-            qa += 0.f + 0.f;
-            const float bs = (float)qb8[e];
-            qf[e] = r16(r16(qa + bs) * CHAIN_ATTN_SCALE);
-        }
+        for (int e = 0; e < DPL; ++e) qf[e] = cross_q_one_slab(s_q[half][sub * DPL + e], qb8[e]);
 #pragma unroll
         for (int kk = 0; kk < KB; ++kk) {
             if (kk >= nb) break;                                               // wave-uniform
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int r = first + kk * STRIDE + u * RPI + rowi;
-                const half8v hv = __builtin_bit_cast(half8v, kv_k[kk][u]);
                 float ks[DPL];
-#pragma unroll
-                for (int e = 0; e < DPL; ++e) ks[e] = r16((float)hv[e] * CHAIN_ATTN_SCALE);
-                float acc = 0.f;
-#pragma unroll
-                for (int e = 0; e < DPL; ++e) acc = fmaf(qf[e], ks[e], acc);
-                acc += wave_dpp<0xB1>(acc);
-                acc += wave_dpp<0x4E>(acc);
-                acc += wave_dpp<0x141>(acc);
-                const float sc = r16(f32_as_is(acc));
+                cross_scaled_key(__builtin_bit_cast(half8v, kv_k[kk][u]), ks);
+                const float sc = cross_row_score(cross_dot8(qf, ks));
                 if (r < nkeys) {
                     if (sub == 0) s_sc[r] = sc;
                     mx = fmaxf(mx, sc);
@@ -799,18 +734,11 @@ __device__ __forceinline__ void chain_cross_stage4(const GemvChainParams& p, con
         for (int kk = 0; kk < KB; ++kk) {
             if (kk >= nb) break;                                               // wave-uniform
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const half8v hv = __builtin_bit_cast(half8v, kv_v[kk][u]);
-#pragma unroll
-                for (int e = 0; e < DPL; ++e) o[e] = fmaf(pr[kk][u], (float)hv[e], o[e]);
-            }
+            for (int u = 0; u < UNR; ++u) pv_row8(pr[kk][u], __builtin_bit_cast(half8v, kv_v[kk][u]), o);
 #pragma unroll
             for (int e = 0; e < DPL; ++e) asm volatile("" : "+v"(o[e]) : : "memory");
         }
-#pragma unroll
-        for (int e = 0; e < DPL; ++e) o[e] += wave_dpp<0x128>(o[e]);
-        wave_add_xor16_x8_nomfma(o);
-        wave_add_xor32_x8_nomfma(o);
+        cross_o_tail8(o);
         if (rowi == 0) {
 #pragma unroll
             for (int e = 0; e < DPL; ++e) s_o[wid][sub * DPL + e] = o[e];
@@ -827,10 +755,9 @@ __device__ __forceinline__ void chain_cross_stage4(const GemvChainParams& p, con
 }
 
 // The merge of the cross-attention's four key-range pieces when they were produced by THIS launch (tagged granules, p.gran_p):
-// attn_cross_combine_kernel's arithmetic -- m = max of the pieces' maxima, f_q = exp(m_q - m), den = sum_q l_q f_q and
-// num = sum_q o_q f_q in piece order, (h16)(num / den) -- with every lane holding all four (m, l) pairs itself instead of taking
-// them from lanes 0-3 (the same values: fmaxf and the products do not depend on who computes them).  All eight waves share the
-// heads (three per wave at 20 heads), a wave's 18 loads are in flight together; the merged row goes to s_in[0].  Ends with a barrier.
+// merge_pieces4 (decode_math.h), with every lane holding all four (m, l) pairs itself where attn_cross_combine_kernel takes them
+// from lanes 0-3.  All eight waves share the heads (three per wave at 20 heads), a wave's 18 loads are in flight together; the
+// merged row goes to s_in[0].  Ends with a barrier.
 template <int NR>
 __device__ __forceinline__ void chain_merge_tagged(const GemvChainParams& p, unsigned tag, h16 (*s_in)[CHAIN_MAX_IN + 8]) {
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -870,15 +797,7 @@ __device__ __forceinline__ void chain_merge_tagged(const GemvChainParams& p, uns
             float mq[4], lq[4], oq[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) { mq[q] = __builtin_bit_cast(float, mb[q]); lq[q] = __builtin_bit_cast(float, lb[q]); oq[q] = __builtin_bit_cast(float, ob[q]); }
-            const float m = fmaxf(fmaxf(mq[0], mq[1]), fmaxf(mq[2], mq[3]));
-            float den = 0.f, num = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float f = __expf(mq[q] - m);
-                den += mul_rn(lq[q], f);                              // (products of their own, as attn_cross_combine_kernel forms them: common.h)
-                num += mul_rn(oq[q], f);
-            }
-            s_in[row][h * 64 + lane] = (h16)(num / den);
+            s_in[row][h * 64 + lane] = merge_pieces4(mq, lq, oq);
         }
     }
     __syncthreads();
@@ -906,17 +825,15 @@ __device__ __forceinline__ int chain_self_prefetch(const GemvChainParams& p, con
 }
 
 // ---- the self-attention of the row as the launch's first stage -----------------------------------------------------------------
-// attn_self_wg_kernel (attn_decode.hip) at one new token of one utterance, for ONE head per workgroup: its four waves are this
-// workgroup's waves 0-3, same expressions in the same order (q / k / v = the qkv sums of the launch before + bias, rounded; the
-// cache append at position T; key blocks of 64 dealt over the waves, a key per lane; the two-pass softmax with fp16 probabilities;
-// P.V by wave-wide 16-byte loads of whole V rows, partial sums added in (wave, row, block) order) -- bit for bit.  The head's 64
-// outputs are published as granules (p.gran_c, tagged with the launch's epoch) for the out projection, this launch's next stage.
+// attn_self_wg_kernel (attn_decode.hip) at one new token of one utterance, for ONE head per workgroup, bit for bit: its four waves
+// are this workgroup's waves 0-3, keys and V rows are dealt over them the same way, partial sums are added in the same (wave, row,
+// block) order and the arithmetic is decode_math.h's.  The head's 64 outputs are published as granules (p.gran_c, tagged with the
+// launch's epoch) for the out projection, this launch's next stage.
 template <bool I8>
 __device__ __forceinline__ void chain_self_stage(const GemvChainParams& p, const ChainLayerArgs& la_, int T, unsigned epoch0, unsigned tag_s, int h, int urow, float* s_p, h16 (*s_new)[64],
                                                  float (*s_r2)[4], float* s_o_flat, float* s_lut, const unsigned char* lds_rows, int lds_v_off) {
     ChainLayerArgs la = la_;                                  // this row's share of the cache ([row][2][H][cap][64])
     la.self_cache = (unsigned char*)la_.self_cache + (size_t)urow * p.self_row_bytes;
-    constexpr float SCALE = 0.35355339059327373f;     // 64^-0.25 (attn_decode.hip: ATTN_SCALE)
     constexpr int ES = I8 ? 1 : 2;
     constexpr int ROW_B = 64 * ES;
     constexpr int DIMS = 16 / ES;
@@ -950,13 +867,13 @@ __device__ __forceinline__ void chain_self_stage(const GemvChainParams& p, const
     if (worker && T > 0 && !in_lds) rows_to_registers();
     const float t_dq = la.self_kv_scale;
     const float inv_t = 1.0f / la.self_kv_scale;
-    // int8 cache: what a cached CODE contributes depends on the code and the layer's scale only -- r16(r16(code * t) * SCALE) to a score,
+    // int8 cache: what a cached CODE contributes depends on the code and the layer's scale only -- r16(r16(code * t) * ATTN_SCALE) to a score,
     // r16(code * t) to P.V (attn_self_wg_kernel's expressions) -- so the 2 x 256 values are computed once per stage (every thread one)
     // and looked up: the same bits, an LDS read instead of seven vector instructions per cached element (64 dims x 11 instructions per
     // key and lane were ~ 1.4 us of the stage; round 5)
     if constexpr (I8) {
         const float d = r16((float)(int)(int8_t)(tid & 255) * t_dq);
-        s_lut[tid] = tid < 256 ? r16(d * SCALE) : d;
+        s_lut[tid] = tid < 256 ? attn_scaled(d) : d;
     }
     float k_new = 0.f, v_new = 0.f;
     if (wid == 0) {                                   // this call's q, k, v of the head (lane = dim): one slab, bias, fp16
@@ -985,14 +902,14 @@ __device__ __forceinline__ void chain_self_stage(const GemvChainParams& p, const
             const float* part = p.self_part + (size_t)urow * 3 * C + h * 64 + lane;
             q += part[0]; k += part[C]; v += part[2 * C];
         }
-        q = r16(q + (la.self_bias ? (float)bq_raw : 0.f));
-        k = r16(k + (la.self_bias ? (float)bk_raw : 0.f));
-        v = r16(v + (la.self_bias ? (float)bv_raw : 0.f));
+        q = qkv_round(q, la.self_bias ? (float)bq_raw : 0.f);
+        k = qkv_round(k, la.self_bias ? (float)bk_raw : 0.f);
+        v = qkv_round(v, la.self_bias ? (float)bv_raw : 0.f);
         s_knew[lane] = (h16)k;
         s_vnew[lane] = (h16)v;
-        if constexpr (I8) s_lut[512 + lane] = r16(k * SCALE);      // the new key's 64 score factors (k is an fp16 value already)
+        if constexpr (I8) s_lut[512 + lane] = attn_scaled(k);      // the new key's 64 score factors
         k_new = k; v_new = v;                         // (the cache append waits for the end of the stage: see there)
-        s_q[lane] = (h16)r16(q * SCALE);
+        s_q[lane] = (h16)attn_scaled(q);
     }
     if (wid >= 4 && in_lds) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the waves that requested the rows: they have landed
     __syncthreads();
@@ -1018,23 +935,21 @@ __device__ __forceinline__ void chain_self_stage(const GemvChainParams& p, const
                             const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
                             for (int e = 0; e < 16; ++e) {
-                                const float kd = s_lut[(ws[e >> 2] >> (8 * (e & 3))) & 0xff];      // = r16(r16((float)code * t_dq) * SCALE)
+                                const float kd = s_lut[(ws[e >> 2] >> (8 * (e & 3))) & 0xff];      // = r16(r16((float)code * t_dq) * ATTN_SCALE)
                                 acc = fmaf((float)s_q[c * 16 + e], kd, acc);
                             }
                         } else {
-                            const half8v wh = __builtin_bit_cast(half8v, w);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) acc = fmaf((float)s_q[c * 8 + e], r16((float)wh[e] * SCALE), acc);
+                            acc = self_score_chunk8(s_q + c * 8, __builtin_bit_cast(half8v, w), acc);
                         }
                     }
                 } else {
-                    if constexpr (I8) {                       // the new key: its 64 factors r16(k * SCALE) wait behind the tables
+                    if constexpr (I8) {                       // the new key: its 64 factors r16(k * ATTN_SCALE) wait behind the tables
 #pragma unroll 8
                         for (int e = 0; e < 64; ++e) acc = fmaf((float)s_q[e], s_lut[512 + e], acc);
                     } else {
                         const h16* kn = s_knew;
 #pragma unroll 8
-                        for (int e = 0; e < 64; ++e) acc = fmaf((float)s_q[e], r16((float)kn[e] * SCALE), acc);
+                        for (int e = 0; e < 64; ++e) acc = fmaf((float)s_q[e], attn_scaled((float)kn[e]), acc);
                     }
                 }
                 sc = r16(f32_as_is(acc));
@@ -1074,9 +989,7 @@ __device__ __forceinline__ void chain_self_stage(const GemvChainParams& p, const
                 for (int d = 0; d < 16; ++d)
                     o[d] = fmaf(pj, s_lut[256 + ((ws[d >> 2] >> (8 * (d & 3))) & 0xff)], o[d]);      // = r16((float)code * t_dq)
             } else {
-                const half8v wh = __builtin_bit_cast(half8v, w);
-#pragma unroll
-                for (int d = 0; d < 8; ++d) o[d] = fmaf(pj, (float)wh[d], o[d]);
+                pv_row8(pj, __builtin_bit_cast(half8v, w), o);
             }
         };
 #pragma unroll
@@ -1119,8 +1032,8 @@ __device__ __forceinline__ void chain_self_stage(const GemvChainParams& p, const
         const size_t off_k = ((size_t)(0 * H + h) * p.self_cap + T) * 64 + lane;
         const size_t off_v = ((size_t)(1 * H + h) * p.self_cap + T) * 64 + lane;
         if (I8) {
-            ((int8_t*)la.self_cache)[off_k] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(k_new * inv_t)));
-            ((int8_t*)la.self_cache)[off_v] = (int8_t)fminf(127.f, fmaxf(-128.f, rintf(v_new * inv_t)));
+            ((int8_t*)la.self_cache)[off_k] = kv_cache_code(k_new, inv_t);
+            ((int8_t*)la.self_cache)[off_v] = kv_cache_code(v_new, inv_t);
         } else {
             ((h16*)la.self_cache)[off_k] = (h16)k_new;
             ((h16*)la.self_cache)[off_v] = (h16)v_new;
