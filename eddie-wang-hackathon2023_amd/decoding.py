@@ -19,7 +19,10 @@ What differs underneath:
   audio features (the reference runs that engine twice per utterance, SURVEY F6);
 * `beam_size` / `patience` select beam search (upstream Whisper's BeamSearchDecoder; the reference carries the options
   but no such class): `BeamSearchDecoder` in the literal loops, wm_beam_step + wm_kv_reorder (csrc/beam.hip) after
-  every decoder launch of `main_loop`.
+  every decoder launch of `main_loop`;
+* `repetition_penalty` / `no_repeat_ngram_size` (CTranslate2 / Hugging Face; repetition.py states the contract): `RepetitionPenalty` and
+  `NoRepeatNGram` first in the filter list of the literal loops, wm_repeat_controls (csrc/repeat.hip) in front of the token step of
+  `main_loop` -- only when one of them is on.
 """
 from __future__ import annotations
 
@@ -40,6 +43,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 import native
+import repetition
 import timing
 from build import get_engine_name
 from session import Session, TensorInfo, str_dtype_to_trt, trt_dtype_to_torch, logger
@@ -65,6 +69,10 @@ class DecodingOptions:
     without_timestamps: bool = False
     max_initial_timestamp: Optional[float] = 1.0
     fp16: bool = True
+    # the in-loop controls against repeated phrases (repetition.py states the contract): they count the tokens a row has SAMPLED --
+    # never the start sequence or a prompt -- and change text tokens only
+    repetition_penalty: float = 1.0     # > 0; logits of sampled text tokens are divided (positive) / multiplied (else) by it; 1.0 = off
+    no_repeat_ngram_size: int = 0       # >= 0; no n-gram of sampled tokens may end in the same text token twice; 0 = off
 
 
 @dataclass(frozen=True)
@@ -166,6 +174,50 @@ class ApplyTimestampRules(LogitFilter):
                                      logits[:, :tb])
 
 
+class RepetitionPenalty(LogitFilter):
+    """The repetition penalty of repetition.py in torch: every distinct text token (id < eot) a row has sampled has its logit
+    divided by the penalty when positive, multiplied otherwise -- once, in fp32, rounded to fp16.  The arithmetic runs on the host
+    whatever device the logits live on: the contract is the correctly rounded IEEE quotient, and a device's elementwise division
+    need not be (a scalar divisor becomes a multiplication by its reciprocal)."""
+
+    def __init__(self, penalty: float, eot: int, sample_begin: int):
+        self.penalty, self.eot, self.sample_begin = float(penalty), eot, sample_begin
+
+    def apply(self, logits: Tensor, tokens: Tensor):
+        sampled = tokens[:, self.sample_begin:].to(logits.device).long()
+        text = (sampled >= 0) & (sampled < self.eot)
+        if self.penalty == 1.0 or not bool(text.any()):
+            return
+        rows, cols = text.nonzero(as_tuple=True)
+        ids = sampled[rows, cols]
+        x = logits[rows, ids].float().cpu()                      # every occurrence reads the logit BEFORE anything is written ...
+        p = torch.tensor(self.penalty, dtype=torch.float32)
+        y = torch.where(x > 0, x / p, x * p).to(logits.dtype)
+        logits[rows, ids] = y.to(logits.device)                  # ... so the occurrences of a token store equal values: penalised once
+
+
+class NoRepeatNGram(LogitFilter):
+    """The no-repeat n-gram rule of repetition.py in torch: with H the tokens a row has sampled and m of them, every text token
+    H[i + n - 1] whose (n - 1)-gram H[i : i + n - 1] equals the last n - 1 tokens is set to -inf.  Matching runs over H as it is
+    (timestamps included); only text tokens (id < eot) are banned."""
+
+    def __init__(self, n: int, eot: int, sample_begin: int):
+        self.n, self.eot, self.sample_begin = int(n), eot, sample_begin
+
+    def apply(self, logits: Tensor, tokens: Tensor):
+        n = self.n
+        sampled = tokens[:, self.sample_begin:].to(logits.device).long()
+        m = sampled.shape[1]
+        if n <= 0 or m < n:                                       # (m == n - 1: the suffix is all of H, no earlier n-gram)
+            return
+        nxt = sampled[:, n - 1:]                                  # H[i + n - 1], i = 0 .. m - n
+        match = torch.ones_like(nxt, dtype=torch.bool)
+        for k in range(n - 1):                                    # H[i + k] == H[m - n + 1 + k]
+            match &= sampled[:, k: k + m - n + 1] == sampled[:, m - n + 1 + k, None]
+        rows, cols = (match & (nxt >= 0) & (nxt < self.eot)).nonzero(as_tuple=True)
+        logits[rows, nxt[rows, cols]] = -np.inf
+
+
 class GreedyDecoder:
     def __init__(self, temperature: float, eot: int):
         self.temperature, self.eot = temperature, eot
@@ -205,6 +257,7 @@ def check_decoding_options(options: DecodingOptions) -> None:
             raise ValueError(f"beam_size * patience = {n} finished candidates per utterance, outside 1..{BEAM_POOL_MAX}")
     elif options.patience is not None:
         raise ValueError("patience requires beam_size to be given")
+    repetition.check_controls(options.repetition_penalty, options.no_repeat_ngram_size)
 
 
 def candidate_mode(options: DecodingOptions, fallback_best_of: Optional[int], temperature: float) -> Tuple[str, int]:
@@ -525,8 +578,11 @@ class _Group:
                                               live_groups=self.live_groups, **counted)
 
     def _token_step(self, logits_ptr, row_stride, cur_len, n_past_dev=None) -> None:
-        """What follows a group's decoder launch: the fused greedy step, or the beam step and the cache reorder."""
+        """What follows a group's decoder launch: the repetition controls where one is on, then the fused greedy step, or the beam
+        step and the cache reorder."""
         dec, call = self.dec, self.call
+        if dec.repeat_controls_on:
+            dec._repeat_controls(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, n_past_dev=n_past_dev)
         if call.beam:
             dec._beam(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, self.kv_table, call.ignore_eot, n_past_dev=n_past_dev)
         else:
@@ -630,7 +686,14 @@ class WhisperDecoding:
         if not only_torch:
             self.positional_embedding = self.positional_embedding.to('cuda').type(torch.float16).contiguous()
 
+        # repetition penalty / no-repeat n-grams (repetition.py): per instance, first in the filter list of the literal loops and one
+        # launch in front of the token step of the device loop (_Group._token_step) -- with the defaults neither exists
+        self.repeat_controls_on = repetition.controls_on(self.options.repetition_penalty, self.options.no_repeat_ngram_size)
         self.logit_filters = []
+        if self.options.repetition_penalty != 1.0:
+            self.logit_filters.append(RepetitionPenalty(self.options.repetition_penalty, self.tokenizer.eot, self.sample_begin))
+        if self.options.no_repeat_ngram_size != 0:
+            self.logit_filters.append(NoRepeatNGram(self.options.no_repeat_ngram_size, self.tokenizer.eot, self.sample_begin))
         self.max_initial_timestamp_index = None
         if self.options.suppress_blank:
             self.logit_filters.append(SuppressBlank(self.tokenizer, self.sample_begin))
@@ -1420,6 +1483,19 @@ class WhisperDecoding:
         io.done, io.n_done = st['done'][lo:hi].data_ptr(), st['n_done'].data_ptr()
         io.row_limit = st['row_limit'][lo:hi].data_ptr()
 
+    def _repeat_controls(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None):
+        """Repetition penalty and no-repeat n-grams (wm_repeat_controls, csrc/repeat.hip) on the raw logits of rows [lo, hi) of the
+        batch state `st`, before the token step: the same rows, tokens and flags as `_fill_rules` hands to it."""
+        io = native.WmRepeatIO()
+        io.logits, io.row_stride = logits_ptr, row_stride
+        io.batch, io.n_vocab = hi - lo, self.decoder_config['vocab_size']
+        io.tokens, io.tokens_ld, io.cur_len = st['tokens'][lo:hi].data_ptr(), st['tokens'].shape[1], cur_len
+        io.n_past_dev = n_past_dev.data_ptr() if n_past_dev is not None else None
+        io.sample_begin, io.eot = self.sample_begin, self.tokenizer.eot
+        io.repetition_penalty, io.no_repeat_ngram_size = float(self.options.repetition_penalty), int(self.options.no_repeat_ngram_size)
+        io.done = st['done'][lo:hi].data_ptr()
+        native.check(native.load_library().wm_repeat_controls(C.byref(io), stream), "wm_repeat_controls")
+
     def _greedy(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None, temperature=None):
         """Fused logit rules + arg-max + append for utterances [lo, hi) of the batch state `st`."""
         io = native.WmGreedyIO()
@@ -1545,6 +1621,9 @@ class WhisperDecoding:
         """What the CU-partitioned schedule does not serve."""
         if not self.cu_partition:
             return
+        if self.repeat_controls_on:
+            raise ValueError("repetition_penalty / no_repeat_ngram_size are not supported by the CU-partitioned schedule (cu_partition = True): "
+                             "it has a loop of its own; use the default loop")
         if n_micro > 1 and self.beam:
             raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")
         if self.block_prefill:

@@ -88,6 +88,7 @@ EXPORTS = (
     "wm_section_cuts_workspace_bytes", "wm_section_cuts",
     "wm_step_finish_group", "wm_attn_cross_group_ex", "wm_decoder_step_group",
     "wm_decoder_prefill_workspace_bytes", "wm_decoder_prefill", "wm_attn_prefill_self", "wm_attn_prefill_cross",
+    "wm_repeat_controls",
 )
 
 
@@ -190,6 +191,21 @@ class WmGreedyIO(C.Structure):
         ("row_limit", C.c_void_p),
         ("temperature", C.c_float), ("row0", C.c_int32),
         ("seed", C.c_uint64), ("seed_dev", C.c_void_p),
+    ]
+
+
+class WmRepeatIO(C.Structure):
+    """wm_repeat_io (include/whisper_mi355.h): repetition penalty and no-repeat n-grams on the raw logits of a token step."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("row_stride", C.c_int64),
+        ("batch", C.c_int32), ("n_vocab", C.c_int32),
+        ("tokens", C.c_void_p), ("tokens_ld", C.c_int32),
+        ("cur_len", C.c_int32),
+        ("n_past_dev", C.c_void_p),
+        ("sample_begin", C.c_int32), ("eot", C.c_int32),
+        ("repetition_penalty", C.c_float),
+        ("no_repeat_ngram_size", C.c_int32),
+        ("done", C.c_void_p),
     ]
 
 
@@ -390,6 +406,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_attn_decode_cross_i8.argtypes = [vp, i32, i32, i32, i32, vp, C.c_float, vp, i32, vp, vp]
     lib.wm_flac_info.argtypes = [vp, sz, C.POINTER(WmFlacStreamInfo)]
     lib.wm_flac_decode.argtypes = [vp, sz, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.wm_repeat_controls.argtypes = [C.POINTER(WmRepeatIO), vp]
     lib.wm_step_advance.argtypes = [vp, vp]
     lib.wm_step_finish.argtypes = [vp, vp, i32, vp, vp]
     lib.wm_beam_workspace_bytes.argtypes = [i32, i32]

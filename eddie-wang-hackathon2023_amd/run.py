@@ -37,11 +37,14 @@ def parse_arguments(argv=None):
                         help="beam search: the beams of an utterance read one copy of its cross-attention K/V (off by default); lets --word_timestamps run with --beam_size")
     parser.add_argument('--word_timestamps', default=False, action='store_true',
                         help='print "start-end word (probability)" lines after the text (cross-attention alignment + DTW on the device; with --beam_size it needs --shared_cross_kv)')
+    parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
+    parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
     return parser.parse_args(argv)
 
 
 def decoding_options(args) -> DecodingOptions:
-    return DecodingOptions(beam_size=args.beam_size, patience=args.patience)
+    return DecodingOptions(beam_size=args.beam_size, patience=args.patience, repetition_penalty=args.repetition_penalty,
+                           no_repeat_ngram_size=args.no_repeat_ngram_size)
 
 
 def load_mel(input_file: str) -> torch.Tensor:
@@ -67,14 +70,15 @@ def real_mel_frames(input_file: str):
 
 def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', input_file: str = 'synthetic',
              vocab: str = None, beam_size: int = None, patience: float = None, word_timestamps: bool = False,
-             shared_cross_kv: bool = False):
+             shared_cross_kv: bool = False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
     logging.basicConfig(level=getattr(logging, log_level.upper(), logging.ERROR))
     torch.cuda.set_device(0)
     mel = load_mel(input_file).to('cuda').type(torch.float16).unsqueeze(0)
     engine_dir = Path(engine_dir)
     whisper_encoding = WhisperEncoding(engine_dir)
-    whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=DecodingOptions(beam_size=beam_size, patience=patience),
-                                       shared_cross_kv=shared_cross_kv)
+    options = DecodingOptions(beam_size=beam_size, patience=patience, repetition_penalty=repetition_penalty,
+                              no_repeat_ngram_size=no_repeat_ngram_size)
+    whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=options, shared_cross_kv=shared_cross_kv)
     begin_time = time.time()
     audio_features = whisper_encoding.get_audio_features(mel)
     languages, language_probs = whisper_decoding.detect_language(audio_features)

@@ -411,23 +411,27 @@ def parse_arguments(argv=None):
     parser.add_argument('--best_of', type=int, default=None,
                         help='samples per window above temperature 0.  Without --beam_size every window is decoded as best_of samples at '
                              'ONE temperature: give exactly one --temperature above 0 (a per-call temperature, i.e. the ladder, is refused)')
+    parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
+    parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
     return parser.parse_args(argv)
 
 
 def build_decoding(args, engine_dir, prompted: bool) -> WhisperDecoding:
     """The WhisperDecoding of the command line: greedy as ever; --beam_size: beam search at 0 and --best_of samples above on one
-    shared copy of the cross K/V; --best_of alone: best_of samples at the one temperature given."""
+    shared copy of the cross K/V; --best_of alone: best_of samples at the one temperature given.  --repetition_penalty /
+    --no_repeat_ngram_size go into the instance's options: every window, temperature and section decodes through it."""
+    repeat = dict(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size)
     if args.beam_size is not None:
-        options = DecodingOptions(language=args.language, beam_size=args.beam_size, patience=args.patience)
+        options = DecodingOptions(language=args.language, beam_size=args.beam_size, patience=args.patience, **repeat)
         return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,
                                fallback_best_of=args.best_of if args.best_of is not None else 1, block_prefill=args.block_prefill)
     if args.patience is not None:
         raise ValueError("--patience needs --beam_size")
     if args.best_of is not None:
-        options = DecodingOptions(language=args.language, best_of=args.best_of, temperature=float(args.temperature[0]))
+        options = DecodingOptions(language=args.language, best_of=args.best_of, temperature=float(args.temperature[0]), **repeat)
         return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,
                                block_prefill=args.block_prefill)
-    return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language), row_prompts=prompted,
+    return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language, **repeat), row_prompts=prompted,
                            block_prefill=args.block_prefill)
 
 

@@ -68,7 +68,8 @@ typedef struct wm_dims {
  *      (still 8: an entry only) wm_forced_probs
  *      (still 8: entries only) wm_section_cuts, wm_section_cuts_workspace_bytes
  *      (still 8: entries and a struct of their own, no existing struct or signature changed) wm_decoder_prefill / wm_prefill_io,
- *      wm_decoder_prefill_workspace_bytes; test-only entries wm_attn_prefill_self, wm_attn_prefill_cross */
+ *      wm_decoder_prefill_workspace_bytes; test-only entries wm_attn_prefill_self, wm_attn_prefill_cross
+ *      (still 8: an entry and a struct of its own) wm_repeat_controls / wm_repeat_io */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -296,6 +297,38 @@ int wm_step_finish(int32_t* counter, const int32_t* done, int batch, int32_t* li
  * list of the utterances that still have a live row: live_groups[0] = their number, live_groups[1..] = their indices, ascending
  * (int32 [1 + batch / group]).  Added under ABI 8 (an entry only). */
 int wm_step_finish_group(int32_t* counter, const int32_t* done, int batch, int group, int32_t* live, int32_t* live_groups, wm_stream_t stream);
+
+/* ---- repetition penalty and no-repeat n-grams (added within ABI 8: an entry and a struct of its own) ----------------
+ * The two controls of CTranslate2 / Hugging Face generation on the raw logits of a token step, in place, BEFORE the logit
+ * filters of wm_greedy_step / wm_beam_step: one launch between the decoder call and the token step (repetition.py states the
+ * contract on the host).  Per row b, H = tokens[b][sample_begin .. cur_len - 1], m = cur_len - sample_begin
+ * tokens: what the row has sampled -- the start sequence and the prompt are not part of it.
+ *   repetition_penalty p (finite, > 0; 1 = off): for every DISTINCT t of H with t < eot, once however often it occurs,
+ *     x = fp32(logits[t]); y = x > 0 ? x / p : x * p as one correctly rounded fp32 operation; logits[t] = fp16(y), round to
+ *     nearest even.  -inf stays -inf.
+ *   no_repeat_ngram_size n (>= 0; 0 = off): if m >= n - 1, for every i in 0 .. m - n with H[i .. i + n - 2] == H[m - n + 1 .. m - 1]
+ *     the token t = H[i + n - 1] is banned if t < eot: logits[t] = -inf.  Matching runs over H as it is, timestamps included;
+ *     n = 1 bans every text token of H.
+ * Penalty first, then bans.  Only text tokens (0 <= id < eot) are ever changed: EOT, the specials and the timestamps belong to
+ * Whisper's own rules.  The log-probabilities the token step books are therefore those of the distribution AFTER the controls,
+ * exactly as they are after the suppress lists.  With both controls off nothing is launched.
+ * Refused (rc 1, nothing launched): a null io / logits / tokens; batch or n_vocab < 1; row_stride < n_vocab with more than one row;
+ * eot outside [0, n_vocab]; p <= 0 or not finite; n < 0; sample_begin outside [0, tokens_ld]; cur_len outside
+ * [sample_begin, tokens_ld]; a history above WM_REPEAT_MAX_HISTORY tokens -- m for a host cur_len, tokens_ld - sample_begin with
+ * n_past_dev (what m can reach: the device value is not known to the host).  Asynchronous on `stream`, no allocation, capturable. */
+#define WM_REPEAT_MAX_HISTORY 512           /* >= n_text_ctx = 448 */
+typedef struct wm_repeat_io {
+    void* logits; int64_t row_stride;         /* fp16, the LAST position's rows; row b starts at logits + b*row_stride elements (any 2-byte address) */
+    int32_t batch, n_vocab;
+    const int32_t* tokens; int32_t tokens_ld; /* int32 [batch][tokens_ld] */
+    int32_t cur_len;                          /* tokens each row holds so far (wm_greedy_io::cur_len) */
+    const int32_t* n_past_dev;                /* optional device step counter: cur_len = *n_past_dev + 1, as wm_greedy_io reads it */
+    int32_t sample_begin, eot;
+    float repetition_penalty;                 /* 1: off */
+    int32_t no_repeat_ngram_size;             /* 0: off */
+    const int32_t* done;                      /* optional int32 [batch]: a row whose flag is set is left untouched */
+} wm_repeat_io;
+int wm_repeat_controls(const wm_repeat_io* io, wm_stream_t stream);
 
 /* ---- beam search step (added within ABI 8: new entries only, no existing struct or signature changed) ----------------
  * The semantics of upstream Whisper's BeamSearchDecoder.update on the device, one call per token step of an utterance
