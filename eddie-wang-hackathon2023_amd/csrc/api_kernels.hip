@@ -247,6 +247,22 @@ int wm_attn_encoder(const void* qkv, int ld, int B, int T, int H, void* out, int
     return launch_attn_encoder(p, (hipStream_t)stream);
 }
 
+// the encoder attention as encoder_forward fills its parameters, max_wgs included (tests/test_gpu_attn_encoder.py)
+int wm_attn_encoder_ex(const wm_attn_encoder_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io, "wm_attn_encoder_ex: null io");
+    WM_REQUIRE(io->qkv, "wm_attn_encoder_ex: null qkv");
+    WM_REQUIRE(io->out, "wm_attn_encoder_ex: null out");
+    WM_REQUIRE(io->B >= 1 && io->T >= 1 && io->H >= 1, "wm_attn_encoder_ex: bad B/T/H (%d, %d, %d)", io->B, io->T, io->H);
+    const int C = io->H * 64;
+    WM_REQUIRE(aligned16(io->qkv), "wm_attn_encoder_ex: qkv must be 16-byte aligned");
+    WM_REQUIRE(((uintptr_t)io->out & 7) == 0, "wm_attn_encoder_ex: out must be 8-byte aligned");
+    WM_REQUIRE(io->ld >= 3 * C && io->ld % 8 == 0, "wm_attn_encoder_ex: ld=%d must be a multiple of 8, >= 3 * H * 64 = %d", io->ld, 3 * C);
+    WM_REQUIRE(io->ldo >= C && io->ldo % 4 == 0, "wm_attn_encoder_ex: ldo=%d must be a multiple of 4, >= H * 64 = %d", io->ldo, C);
+    WM_REQUIRE(io->max_wgs >= 0, "wm_attn_encoder_ex: max_wgs=%d must not be negative", io->max_wgs);
+    AttnEncParams p{(const h16*)io->qkv, io->ld, io->B, io->T, io->H, (h16*)io->out, io->ldo, io->max_wgs};
+    return launch_attn_encoder(p, (hipStream_t)stream);
+}
+
 int wm_attn_decode_cross(const float* q, int B, int L, int H, int Tk, const void* kv, void* out, int nsplit,
                          float* ws, wm_stream_t stream) {
     AttnCrossParams p{};

@@ -89,6 +89,7 @@ EXPORTS = (
     "wm_step_finish_group", "wm_attn_cross_group_ex", "wm_decoder_step_group",
     "wm_decoder_prefill_workspace_bytes", "wm_decoder_prefill", "wm_attn_prefill_self", "wm_attn_prefill_cross",
     "wm_repeat_controls",
+    "wm_attn_encoder_ex",
 )
 
 
@@ -303,6 +304,16 @@ class WmAttnCrossGroupIO(C.Structure):
     _fields_ = WmAttnCrossIO._fields_ + [("G", C.c_int32), ("live_utt", C.c_void_p)]
 
 
+class WmAttnEncoderIO(C.Structure):
+    """wm_attn_encoder_io (include/whisper_mi355.h): the encoder attention with every field the encoder engine sets (tests)."""
+    _fields_ = [
+        ("qkv", C.c_void_p), ("ld", C.c_int32),
+        ("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32),
+        ("out", C.c_void_p), ("ldo", C.c_int32),
+        ("max_wgs", C.c_int32),
+    ]
+
+
 class WmTapIO(C.Structure):
     """wm_tap_io (include/whisper_mi355.h): where wm_decoder_step_tap writes the cross-attention queries."""
     _fields_ = [("q_tape", C.c_void_p), ("capacity", C.c_int32), ("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32)]
@@ -419,6 +430,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_attn_self_ex.argtypes = [C.POINTER(WmAttnSelfIO), vp]
     lib.wm_attn_cross_ex.argtypes = [C.POINTER(WmAttnCrossIO), vp]
     lib.wm_attn_cross_group_ex.argtypes = [C.POINTER(WmAttnCrossGroupIO), vp]
+    lib.wm_attn_encoder_ex.argtypes = [C.POINTER(WmAttnEncoderIO), vp]
     lib.wm_step_finish_group.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.wm_embed.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp]
     lib.wm_mel_transpose_pad.argtypes = [vp, i32, i32, i32, vp, vp]

@@ -69,7 +69,8 @@ typedef struct wm_dims {
  *      (still 8: entries only) wm_section_cuts, wm_section_cuts_workspace_bytes
  *      (still 8: entries and a struct of their own, no existing struct or signature changed) wm_decoder_prefill / wm_prefill_io,
  *      wm_decoder_prefill_workspace_bytes; test-only entries wm_attn_prefill_self, wm_attn_prefill_cross
- *      (still 8: an entry and a struct of its own) wm_repeat_controls / wm_repeat_io */
+ *      (still 8: an entry and a struct of its own) wm_repeat_controls / wm_repeat_io
+ *      (still 8: a test-only entry and a struct of its own) wm_attn_encoder_ex / wm_attn_encoder_io */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -564,6 +565,23 @@ typedef struct wm_attn_cross_group_io {
     const int32_t* live_utt;
 } wm_attn_cross_group_io;
 int wm_attn_cross_group_ex(const wm_attn_cross_group_io* io, wm_stream_t stream);
+/* The encoder attention kernel (csrc/attn_encoder.hip) with every field of AttnEncParams that the encoder engine sets, reachable alone
+ * (tests/test_gpu_attn_encoder.py; wm_attn_encoder below has no max_wgs).  Not used by the product path.  qkv fp16 [B * T][ld], columns
+ * q | k | v of H * 64 each (q, k pre-scaled by 64^-0.25, as the QKV epilogue leaves them), columns 3 * H * 64 .. ld - 1 are not read;
+ * out fp16 [B * T][ldo], columns H * 64 .. ldo - 1 are not written.  max_wgs as wm_encoder_forward_shared passes it (2 * cu_budget):
+ * > 0 and below the B * H * ceil(T / 256) items of a T > 128 launch: the persistent form on at most that many workgroups (rounded
+ * down to a multiple of 8 from 8 on); otherwise, and always with 0, the plain launch.  The lab knob WM_ATTN_MAX_WGS is consulted
+ * only with max_wgs == 0, as by wm_attn_encoder.
+ * Refused (rc 1, nothing launched): a null io / qkv / out; qkv not 16-byte aligned; out not 8-byte aligned; ld < 3 * H * 64 or not
+ * a multiple of 8; ldo < H * 64 or not a multiple of 4; B, T or H < 1; max_wgs < 0.  Added under ABI 8 (an entry and a struct of
+ * its own). */
+typedef struct wm_attn_encoder_io {
+    const void* qkv; int32_t ld;
+    int32_t B, T, H;
+    void* out; int32_t ldo;
+    int32_t max_wgs;
+} wm_attn_encoder_io;
+int wm_attn_encoder_ex(const wm_attn_encoder_io* io, wm_stream_t stream);
 /* x[r] = fp16(E[token of row r] + pos[r % L + T]), r < M = B * L; token of row r = tokens[(r / L) * tokens_ld + r % L + T];
  * T = *t_dev when given, else 0.  emb_tiles: the fp16 embedding in tile-linear layout (weight.py: tile_linear), C a multiple
  * of 32; token ids are clamped to [0, n_vocab).  generation (optional): incremented once per call. */

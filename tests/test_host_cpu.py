@@ -45,7 +45,8 @@ def test_struct_layouts_match_header(tmp_path):
               "wm_gemm_io": [n for n, _ in native.WmGemmIO._fields_],
               "wm_row_finish_io": [n for n, _ in native.WmRowFinishIO._fields_],
               "wm_attn_self_io": [n for n, _ in native.WmAttnSelfIO._fields_],
-              "wm_attn_cross_io": [n for n, _ in native.WmAttnCrossIO._fields_]}
+              "wm_attn_cross_io": [n for n, _ in native.WmAttnCrossIO._fields_],
+              "wm_attn_encoder_io": [n for n, _ in native.WmAttnEncoderIO._fields_]}
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "whisper_mi355.h"', 'int main(void){']
     for s, fs in fields.items():
         src.append(f'printf("{s} %zu\\n", sizeof({s}));')
@@ -58,7 +59,8 @@ def test_struct_layouts_match_header(tmp_path):
     for s, cls in (("wm_dims", native.WmDims), ("wm_decoder_io", native.WmDecoderIO), ("wm_greedy_io", native.WmGreedyIO),
                    ("wm_gemv_io", native.WmGemvIO), ("wm_chain_status", native.WmChainStatus),
                    ("wm_gemm_io", native.WmGemmIO), ("wm_row_finish_io", native.WmRowFinishIO),
-                   ("wm_attn_self_io", native.WmAttnSelfIO), ("wm_attn_cross_io", native.WmAttnCrossIO)):
+                   ("wm_attn_self_io", native.WmAttnSelfIO), ("wm_attn_cross_io", native.WmAttnCrossIO),
+                   ("wm_attn_encoder_io", native.WmAttnEncoderIO)):
         assert int(got[s]) == C.sizeof(cls), s
         for f in fields[s]:
             assert int(got[f"{s}.{f}"]) == getattr(cls, f).offset, f"{s}.{f}"
