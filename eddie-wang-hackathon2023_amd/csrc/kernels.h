@@ -187,6 +187,14 @@ size_t section_cuts_workspace_bytes(int batch, long long total_frames);
 int launch_section_cuts(const void* const* src, const int32_t* src_ld, const int32_t* content, int batch, int n_mels, int lo,
                         int hi, int h, int32_t* cuts, int cuts_ld, int32_t* n_cuts, void* workspace, long long total_frames,
                         hipStream_t stream);
+// speech.hip: the speech spans of a ragged batch of whole-file log-mels (speech.py: floor, flags, runs, join, drop, pad) and the
+// packed mels: the spans' columns in order, then n_pad copies of the file's last column
+size_t speech_spans_workspace_bytes(int batch, long long total_frames);
+int launch_speech_spans(const void* const* src, const int32_t* src_ld, const int32_t* content, int batch, int n_mels, int h, int step,
+                        int permille, int min_silence, int min_speech, int pad, int32_t* spans, int spans_ld, int32_t* n_spans,
+                        void* workspace, long long total_frames, hipStream_t stream);
+int launch_mel_gather(const void* const* src, const int32_t* src_ld, const int32_t* spans, const int32_t* n_spans, int spans_ld,
+                      int batch, int n_mels, int n_pad, void* const* dst, const int32_t* dst_ld, hipStream_t stream);
 int launch_layernorm(const h16* x, int ldx, int M, int N, const h16* g, const h16* b, h16* out, int ldo,
                      hipStream_t stream);
 

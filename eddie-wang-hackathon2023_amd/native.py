@@ -86,6 +86,7 @@ EXPORTS = (
     "wm_attn_self_ex", "wm_attn_cross_ex",
     "wm_forced_probs",
     "wm_section_cuts_workspace_bytes", "wm_section_cuts",
+    "wm_speech_spans_workspace_bytes", "wm_speech_spans", "wm_mel_gather",
     "wm_step_finish_group", "wm_attn_cross_group_ex", "wm_decoder_step_group",
     "wm_decoder_prefill_workspace_bytes", "wm_decoder_prefill", "wm_attn_prefill_self", "wm_attn_prefill_cross",
     "wm_repeat_controls",
@@ -441,6 +442,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_section_cuts_workspace_bytes.argtypes = [i32, C.c_int64]
     lib.wm_section_cuts_workspace_bytes.restype = sz
     lib.wm_section_cuts.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, C.c_int64, vp]
+    lib.wm_speech_spans_workspace_bytes.argtypes = [i32, C.c_int64]
+    lib.wm_speech_spans_workspace_bytes.restype = sz
+    lib.wm_speech_spans.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, C.c_int64, vp]
+    lib.wm_mel_gather.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.wm_decoder_step_tap.argtypes = [vp, C.POINTER(WmDecoderIO), C.POINTER(WmTapIO), vp]
     lib.wm_align_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.wm_align_workspace_bytes.restype = sz

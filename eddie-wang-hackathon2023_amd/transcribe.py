@@ -33,18 +33,27 @@ longform.py states the contract (the rules and the schedule, on the host, tested
     segments are shifted and joined by sections.merge_sections.  Unlike upstream, nothing crosses a cut: sections run side by
     side, so `condition_on_previous_text` keeps its history per section.  Without the option nothing of this runs.
 
+  * `speech` (speech.SpeechOptions): skip silence.  The frames that an energy rule over the log-mel takes
+    for speech are found on the device (wm_speech_spans, csrc/speech.hip: one launch and one copy back for all files), packed
+    into shorter files (wm_mel_gather: one launch) and transcribed by everything above -- sections included: the cuts are found
+    on the packed mel -- and speech.restore moves every time back into the original file.  The decoder never sees the quiet
+    stretches, so it cannot invent text over them, and a file with 40 % pauses has 40 % fewer windows.  An energy rule, not a
+    trained voice-activity model, and its defaults are parameters, not measurements.  Without the option nothing of this runs.
+
 Refused (ValueError): an instance built with `prompt` / `prefix` (use `initial_prompt`), conditioning or an initial prompt on
 an instance without `row_prompts`, beam_size / best_of together with a ladder of more than one temperature, and word timestamps
 with beam_size / best_of -- unless the instance shares its cross K/V (WhisperDecoding(shared_cross_kv=True): word timestamps for
 candidates) and names its sampling mode (beam_size with fallback_best_of: beam search at temperature 0, samples above -- upstream's
 `whisper audio.wav` recipe with the full ladder, conditioning and sections; best_of alone keeps the one-temperature rule); word
 timestamps on an engine with int8 cross K/V raise WhisperDecoding.word_timestamps' own error.  Out of
-scope: clip_timestamps, the hallucination-silence heuristics (hallucination_silence_threshold).  Files at any rate from 4 kHz to 192 kHz and with
+scope: clip_timestamps, the hallucination-silence heuristics (hallucination_silence_threshold; `speech` removes silence ahead of
+the decoder instead), a learned voice-activity model.  Files at any rate from 4 kHz to 192 kHz and with
 several channels are downmixed and resampled to 16 kHz on the device (whisper_utils.load_audio_device, wm_resample).
 
 CLI: python transcribe.py --engine_dir eng --input_file a.flac [b.flac ...] --vocab multilingual.tiktoken [--temperature T ...]
 [--no_fallback] [--condition_on_previous_text] [--initial_prompt TEXT] [--word_timestamps] [--sections [--section_seconds S]
-[--min_section_seconds S]] [--beam_size K [--patience P]] [--best_of M] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
+[--min_section_seconds S]] [--skip_silence [--silence_margin_db D] [--min_silence_seconds S] [--min_speech_seconds S]
+[--speech_pad_seconds S]] [--beam_size K [--patience P]] [--best_of M] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
 line per non-empty segment, and with --word_timestamps one "start-end word (probability)" line per word under it.
 """
 from __future__ import annotations
@@ -62,9 +71,11 @@ import torch
 import longform
 import native
 import sections as sections_mod
+import speech as speech_mod
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 from sections import SectionOptions
+from speech import SpeechOptions
 from tokenizer import Tokenizer
 
 
@@ -168,6 +179,79 @@ def section_cuts(mels: Sequence[torch.Tensor], content_frames: Sequence[int], op
     return [host[n + f * cuts_ld: n + f * cuts_ld + found[f]] for f in range(n)]
 
 
+def _mel_table(mels: Sequence[torch.Tensor], content_frames: Sequence[int], what: str):
+    """(device int64 [3, n]: pointers, row lengths, content frames; n_mels) of a ragged batch of whole-file mels."""
+    if len(content_frames) != len(mels):
+        raise ValueError(f"{what}: {len(content_frames)} content_frames for {len(mels)} mels")
+    n_mels = int(mels[0].shape[0])
+    for m, c in zip(mels, content_frames):
+        assert m.is_cuda and m.dtype == torch.float16 and m.dim() == 2 and m.shape[0] == n_mels and m.is_contiguous(), \
+            "a mel must be a contiguous fp16 [n_mels, frames] tensor on the GPU"
+        if not 0 <= c <= m.shape[1]:
+            raise ValueError(f"{what}: {c} frames of content in a mel of {m.shape[1]}")
+    table = torch.tensor([[m.data_ptr() for m in mels], [m.shape[1] for m in mels], [int(c) for c in content_frames]],
+                         dtype=torch.int64).to(mels[0].device, non_blocking=False)
+    return table, n_mels
+
+
+def speech_spans(mels: Sequence[torch.Tensor], content_frames: Sequence[int], options: SpeechOptions,
+                 window: int = 3000) -> List[List[tuple]]:
+    """The speech spans [(a, b), ...] of every file in frames, ascending (speech.speech_spans_ref on the device: ONE wm_speech_spans
+    launch for all files on the current stream and one copy of the spans and their counts back).  mels[f]: contiguous fp16
+    [n_mels, >= content_frames[f]] on the GPU; `window`: the model's 2 * n_audio_ctx, which fixes the seconds per frame."""
+    n = len(mels)
+    if n == 0:
+        return []
+    table, n_mels = _mel_table(mels, content_frames, "speech_spans")
+    h, step, permille, min_silence, min_speech, pad = options.frames(window, n_mels)
+    dev = mels[0].device
+    total = int(sum(content_frames))
+    # rule (b) leaves gaps of at least min_silence frames between spans of at least one frame, and (c), (d) only take spans away
+    spans_ld = max(1, (max(int(c) for c in content_frames) + min_silence) // (1 + min_silence))
+    ld, content = table[1].to(torch.int32), table[2].to(torch.int32)
+    lib = native.load_library()
+    ws_bytes = int(lib.wm_speech_spans_workspace_bytes(n, total))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(n * (1 + 2 * spans_ld), dtype=torch.int32, device=dev)        # n_spans [n], then spans [n][spans_ld][2]
+    native.check(lib.wm_speech_spans(table[0].data_ptr(), ld.data_ptr(), content.data_ptr(), n, n_mels, h, step, permille,
+                                     min_silence, min_speech, pad, out[n:].data_ptr(), spans_ld, out.data_ptr(), ws.data_ptr(),
+                                     ws_bytes, total, torch.cuda.current_stream(dev).cuda_stream), "wm_speech_spans")
+    host = out.cpu().tolist()
+    found = host[:n]
+    if any(k < 0 or k > spans_ld for k in found):
+        raise ValueError(f"speech_spans: wm_speech_spans found {found} spans, room for {spans_ld} per file")
+    flat = [host[n + 2 * f * spans_ld: n + 2 * (f * spans_ld + found[f])] for f in range(n)]
+    return [list(zip(x[0::2], x[1::2])) for x in flat]
+
+
+def packed_mels(mels: Sequence[torch.Tensor], content_frames: Sequence[int], spans: Sequence[Sequence[tuple]], window: int):
+    """(packed mels, their content frames P): per file the columns of its spans in order, then `window` copies of its last column
+    -- speech.packed_mel_ref's bit for bit, [n_mels, P + window] each -- from ONE wm_mel_gather launch for all files."""
+    n = len(mels)
+    if n == 0:
+        return [], []
+    if len(spans) != n:
+        raise ValueError(f"packed_mels: {len(spans)} span lists for {n} mels")
+    table, n_mels = _mel_table(mels, content_frames, "packed_mels")
+    for m, c, sp in zip(mels, content_frames, spans):
+        if m.shape[1] < 1:
+            raise ValueError("packed_mels: a mel without frames")
+        speech_mod.check_spans(sp, int(c))
+    dev = mels[0].device
+    packed = [sum(b - a for a, b in sp) for sp in spans]
+    out = [torch.empty((n_mels, P + window), dtype=torch.float16, device=dev) for P in packed]
+    spans_ld = max(1, max(len(sp) for sp in spans))
+    flat = [[v for a, b in sp for v in (a, b)] + [0] * (2 * (spans_ld - len(sp))) for sp in spans]
+    ints = torch.tensor([len(sp) for sp in spans] + [P + window for P in packed] + [v for row in flat for v in row],
+                        dtype=torch.int32).to(dev, non_blocking=False)              # n_spans [n], dst_ld [n], spans [n][spans_ld][2]
+    dst = torch.tensor([o.data_ptr() for o in out], dtype=torch.int64).to(dev, non_blocking=False)
+    ld = table[1].to(torch.int32)
+    native.check(native.load_library().wm_mel_gather(table[0].data_ptr(), ld.data_ptr(), ints[2 * n:].data_ptr(), ints.data_ptr(),
+                                                     spans_ld, n, n_mels, window, dst.data_ptr(), ints[n:].data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream), "wm_mel_gather")
+    return out, packed
+
+
 def section_mels(mels: Sequence[torch.Tensor], content_frames: Sequence[int], cuts: Sequence[Sequence[int]], window: int):
     """The sections of every file as files of their own: (section mels, their content frames, owner, starts) in file order and
     section order; owner[i] is the file of section i and starts[i] its first frame there.  A section's mel is
@@ -188,7 +272,7 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
                    compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
                    no_speech_threshold: Optional[float] = 0.6, n_rows: Optional[int] = None, trace: Optional[list] = None,
                    condition_on_previous_text: bool = False, initial_prompt=None, word_timestamps: bool = False,
-                   sections: Optional[SectionOptions] = None) -> List[dict]:
+                   sections: Optional[SectionOptions] = None, speech: Optional[SpeechOptions] = None) -> List[dict]:
     """Transcribe files given as log-mels: mels[f] fp16 [n_mels, content_frames[f] + W] on the GPU (W = 2 * n_audio_ctx; the last
     W frames are the log-mel of 30 s of padding: whisper_utils.long_log_mel_device).  One dict per file: language, text, segments;
     a segment: seek, start, end (seconds), text, tokens, temperature, avg_logprob, compression_ratio, no_speech_prob.
@@ -203,13 +287,48 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
     `sections`: cut every file where it is quietest and decode the sections side by side (module docstring; sections.py).  The
     rows' "files" are then the sections, in file order and section order -- `n_rows` defaults to min(sections, what fits), and
     `trace` speaks of sections; a file's result also carries "sections": [(start, end), ...] in seconds.  Unlike upstream,
-    `condition_on_previous_text` keeps its history per section: the sections run side by side, so no text crosses a cut."""
+    `condition_on_previous_text` keeps its history per section: the sections run side by side, so no text crosses a cut.
+    `speech`: skip silence (module docstring; speech.py) -- the spans an energy rule takes for speech are packed into shorter
+    files, those are transcribed as above (`trace`, `seek` inside it and the sections' cuts speak of the packed files), and every
+    time of the result is moved back into the original file (speech.restore); a file's result also carries "speech":
+    [(start, end), ...] in seconds.  A file without speech has no segments, an empty text and the language the options name
+    (None if none is named)."""
     kw = dict(temperatures=temperatures, compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
               no_speech_threshold=no_speech_threshold, n_rows=n_rows, trace=trace, condition_on_previous_text=condition_on_previous_text,
               initial_prompt=initial_prompt, word_timestamps=word_timestamps)
+    if speech is not None:
+        return _transcribe_speech(encoding, decoding, mels, content_frames, speech, sections, **kw)
     if sections is not None:
         return _transcribe_sections(encoding, decoding, mels, content_frames, sections, **kw)
     return _transcribe_files(encoding, decoding, mels, content_frames, None, **kw)
+
+
+def _transcribe_speech(encoding, decoding, mels, content_frames, options: SpeechOptions, sections, **kw) -> List[dict]:
+    """transcribe_mel with `speech`: find the spans, pack them, transcribe the packed files, move the times back."""
+    n_files = len(mels)
+    if len(content_frames) != n_files:
+        raise ValueError(f"transcribe: {len(content_frames)} content_frames for {n_files} mels")
+    ladder = kw['temperatures']
+    check_supported(decoding, tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])),
+                    kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
+    if n_files == 0:
+        return []
+    W = 2 * decoding.decoder_config['num_audio_ctx']
+    fs = longform.CHUNK_LENGTH / W
+    mels = [m.to(torch.float16).contiguous() for m in mels]
+    content_frames = [int(c) for c in content_frames]
+    spans = speech_spans(mels, content_frames, options, window=W)
+    packed, packed_frames = packed_mels(mels, content_frames, spans, W)
+    if sections is not None:
+        results = _transcribe_sections(encoding, decoding, packed, packed_frames, sections, **kw)
+    else:
+        results = _transcribe_files(encoding, decoding, packed, packed_frames, None, **kw)
+    for r, sp in zip(results, spans):
+        r['segments'] = speech_mod.restore(r['segments'], sp, fs)
+        r['speech'] = [(a * fs, b * fs) for a, b in sp]
+        if 'sections' in r:
+            r['sections'] = [(speech_mod.restore_time(a, sp, fs), speech_mod.restore_time(b, sp, fs, end=True)) for a, b in r['sections']]
+    return results
 
 
 def _transcribe_sections(encoding, decoding, mels, content_frames, options: SectionOptions, **kw) -> List[dict]:
@@ -404,6 +523,14 @@ def parse_arguments(argv=None):
                              '(no text or timestamp crosses a cut; conditioning keeps its history per section)')
     parser.add_argument('--section_seconds', type=float, default=SectionOptions.max_seconds, help='longest section (default: 30)')
     parser.add_argument('--min_section_seconds', type=float, default=None, help='shortest section but for the last (default: half the longest)')
+    parser.add_argument('--skip_silence', default=False, action='store_true',
+                        help='cut out what an energy rule over the log-mel takes for silence before anything is decoded, and move the '
+                             'timestamps back (not a trained voice-activity model; the defaults are untuned parameters)')
+    parser.add_argument('--silence_margin_db', type=float, default=SpeechOptions.margin_db,
+                        help="speech stands this far above the file's loudness floor (default: 8)")
+    parser.add_argument('--min_silence_seconds', type=float, default=SpeechOptions.min_silence_seconds, help='shorter pauses stay in (default: 2)')
+    parser.add_argument('--min_speech_seconds', type=float, default=SpeechOptions.min_speech_seconds, help='shorter speech goes (default: 0.25)')
+    parser.add_argument('--speech_pad_seconds', type=float, default=SpeechOptions.speech_pad_seconds, help='kept on either side of speech (default: 0.4)')
     parser.add_argument('--beam_size', type=int, default=None,
                         help='beam search at temperature 0 with this many beams (default: greedy); the beams share one copy of the cross K/V, '
                              'and above temperature 0 the ladder draws --best_of samples per window (default 1), at most beam_size')
@@ -446,10 +573,15 @@ def main(args) -> List[dict]:
     results = transcribe(encoding, decoding, args.input_file, temperatures=temperatures, n_rows=args.rows,
                          condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt,
                          word_timestamps=args.word_timestamps,
-                         sections=SectionOptions(args.section_seconds, args.min_section_seconds) if args.sections else None)
+                         sections=SectionOptions(args.section_seconds, args.min_section_seconds) if args.sections else None,
+                         **(dict(speech=SpeechOptions(margin_db=args.silence_margin_db, min_silence_seconds=args.min_silence_seconds,
+                                                      min_speech_seconds=args.min_speech_seconds,
+                                                      speech_pad_seconds=args.speech_pad_seconds)) if args.skip_silence else {}))
     for path, result in zip(args.input_file, results):
         if len(results) > 1:
             print(f"{path} ({result['language']})")
+        if args.skip_silence:
+            print("speech: " + (", ".join(f"{format_timestamp(a)} --> {format_timestamp(b)}" for a, b in result['speech']) or "none"))
         for s in result['segments']:
             if s['text'].strip():
                 print(f"[{format_timestamp(s['start'])} --> {format_timestamp(s['end'])}] {s['text'].strip()}")

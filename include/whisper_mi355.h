@@ -67,6 +67,7 @@ typedef struct wm_dims {
  *      wm_step_finish_group, wm_attn_cross_group_ex
  *      (still 8: an entry only) wm_forced_probs
  *      (still 8: entries only) wm_section_cuts, wm_section_cuts_workspace_bytes
+ *      (still 8: entries only) wm_speech_spans, wm_speech_spans_workspace_bytes, wm_mel_gather
  *      (still 8: entries and a struct of their own, no existing struct or signature changed) wm_decoder_prefill / wm_prefill_io,
  *      wm_decoder_prefill_workspace_bytes; test-only entries wm_attn_prefill_self, wm_attn_prefill_cross
  *      (still 8: an entry and a struct of its own) wm_repeat_controls / wm_repeat_io
@@ -622,6 +623,34 @@ size_t wm_section_cuts_workspace_bytes(int batch, int64_t total_frames);
 int wm_section_cuts(const void* const* src, const int32_t* src_ld, const int32_t* content, int batch, int n_mels, int lo, int hi,
                     int h, int32_t* cuts, int cuts_ld, int32_t* n_cuts, void* workspace, size_t workspace_bytes,
                     int64_t total_frames, wm_stream_t stream);
+/* The speech of long files, so that the quiet stretches can be cut out before anything is decoded (speech.py states the contract;
+ * DESIGN.md section 5j).  Per file b, in integers, with F = content[b], x = src[b] and q, s as in wm_section_cuts:
+ *   floor = sorted(s)[min(F - 1, F * permille / 1000)]                                   (an exact order statistic)
+ *   v[t]  = (int64)s[t] - floor >= n_mels * (2h + 1) * step
+ *   spans = the maximal runs [a, b) of v; neighbours with a gap < min_silence joined; spans shorter than min_speech dropped; each
+ *           widened to [max(0, a - pad), min(F, b + pad)) and joined where they now touch or overlap.
+ * spans[(b * spans_ld + i) * 2 + {0, 1}] are the first frame and the end of span i of file b for i < n_spans[b].  The conventions are
+ * wm_section_cuts': device arrays of pointers, strides and lengths; a null or empty file reports n_spans = 0; a file that has frames
+ * and ends beyond total_frames, or that has more than spans_ld spans, reports n_spans = -1, and nothing is written outside a file's
+ * spans_ld entries (with min_silence the spans number (F + min_silence) / (1 + min_silence) at most).  Requires 1 <= step <= 32768,
+ * 0 <= permille <= 1000, min_silence >= 1, min_speech >= 1, pad >= 0, h >= 0 and n_mels * (2h + 1) < 131072.  The workspace
+ * (wm_speech_spans_workspace_bytes, 8-byte aligned) needs no initialisation.  Asynchronous on `stream`: no allocation, no host
+ * synchronisation, capturable.  Added under ABI 8 (entries only; no struct changes). */
+size_t wm_speech_spans_workspace_bytes(int batch, int64_t total_frames);
+int wm_speech_spans(const void* const* src, const int32_t* src_ld, const int32_t* content, int batch, int n_mels, int h, int step,
+                    int permille, int min_silence, int min_speech, int pad, int32_t* spans, int spans_ld, int32_t* n_spans,
+                    void* workspace, size_t workspace_bytes, int64_t total_frames, wm_stream_t stream);
+/* The packed log-mels of a ragged batch, one launch for all files:
+ *   dst[b][m * dst_ld[b] + p] = src[b][m * src_ld[b] + a_k + (p - P_k)]    for P_k <= p < P_k + (b_k - a_k), span k of file b
+ *   dst[b][m * dst_ld[b] + P + j] = src[b][m * src_ld[b] + src_ld[b] - 1]  for j < n_pad, P the packed frames of the file
+ * over the spans TAKEN from spans[(b * spans_ld + k) * 2 + {0, 1}], k < min(max(n_spans[b], 0), spans_ld): span k is taken if
+ * 0 <= a_k < b_k <= src_ld[b] and a_k >= b_j for every earlier span j that lies in that range; any other span is skipped and never
+ * dereferenced, and P_k counts the spans taken only.  Elements with p >= dst_ld[b] are not written; elements of dst that no rule
+ * above names are left as they are.  src, dst: DEVICE arrays of `batch` device pointers (a null entry, src_ld < 1 or dst_ld < 1:
+ * the file is skipped); src_ld, dst_ld, n_spans, spans: DEVICE int32.  Rows may start at any 2-byte address.  Asynchronous on
+ * `stream`: no allocation, no host synchronisation, capturable.  Added under ABI 8 (an entry only; no struct changes). */
+int wm_mel_gather(const void* const* src, const int32_t* src_ld, const int32_t* spans, const int32_t* n_spans, int spans_ld,
+                  int batch, int n_mels, int n_pad, void* const* dst, const int32_t* dst_ld, wm_stream_t stream);
 /* zeroes rows 0 and Tpad - 1 of every utterance of buf fp16 [B][Tpad][C]. */
 int wm_zero_pad_rows(void* buf, int B, int Tpad, int C, wm_stream_t stream);
 /* ids[b] = arg-max of row b of fp16 logits (first index wins ties).  The decode loop itself uses
