@@ -22,7 +22,10 @@ What differs underneath:
   every decoder launch of `main_loop`;
 * `repetition_penalty` / `no_repeat_ngram_size` (CTranslate2 / Hugging Face; repetition.py states the contract): `RepetitionPenalty` and
   `NoRepeatNGram` first in the filter list of the literal loops, wm_repeat_controls (csrc/repeat.hip) in front of the token step of
-  `main_loop` -- only when one of them is on.
+  `main_loop` -- only when one of them is on;
+* `hotwords` / `sequence_bias` (contextual biasing / Hugging Face; biasing.py states the contract and builds the table): `SequenceBias`
+  directly behind the two repetition filters of the literal loops, wm_sequence_bias (csrc/bias.hip) behind wm_repeat_controls in the
+  token step of `main_loop` -- only on an instance built with a bias; `set_bias` rewrites the table between calls.
 
 This module holds the options, the results and `WhisperDecoding`'s construction and call contract (start rows, prompts, post_process).
 host_decoding.py holds the literal loops and the host filter / decoder classes and imports neither `native` nor `ctypes`;
@@ -42,13 +45,14 @@ import numpy as np
 import torch
 from torch import Tensor
 
+import biasing
 import repetition
 from build import get_engine_name
 from device_loop import (DeviceLoop, call_key, fork, groups_run_alone, join, language_key, partition_key,  # noqa: F401 (re-exported)
                          prefill_key, step_key, steps_side_by_side)
 from host_decoding import (BEAM_MAX, BEAM_POOL_MAX, CHUNK_LENGTH, ApplyTimestampRules, BeamSearchDecoder,  # noqa: F401 (re-exported)
                            GreedyDecoder, HostLoops, LogitFilter, MaximumLikelihoodRanker, NoRepeatNGram, RepetitionPenalty,
-                           SuppressBlank, SuppressTokens)
+                           SequenceBias, SuppressBlank, SuppressTokens)
 from session import Session
 from tokenizer import Tokenizer
 
@@ -74,6 +78,12 @@ class DecodingOptions:
     # never the start sequence or a prompt -- and change text tokens only
     repetition_penalty: float = 1.0     # > 0; logits of sampled text tokens are divided (positive) / multiplied (else) by it; 1.0 = off
     no_repeat_ngram_size: int = 0       # >= 0; no n-gram of sampled tokens may end in the same text token twice; 0 = off
+    # the in-loop bias on vocabulary (biasing.py states the contract): one table per instance, matched against the tokens a row has
+    # SAMPLED, applied behind the repetition controls and in front of Whisper's own rules; one bias per token, never a sum
+    hotwords: Optional[Tuple[Union[str, Tuple[int, ...]], ...]] = None      # phrases boosted at every position: strings and / or token tuples
+    hotword_bias: float = 3.0           # added to the token that continues a hotword (a parameter, not a measurement)
+    hotword_start_bias: float = 1.5     # added to the first token of a hotword, at every step
+    sequence_bias: Optional[Tuple[Tuple[Tuple[int, ...], float], ...]] = None   # ((token tuple, bias), ...): the token that completes a sequence
 
 
 @dataclass(frozen=True)
@@ -104,6 +114,7 @@ def check_decoding_options(options: DecodingOptions) -> None:
     elif options.patience is not None:
         raise ValueError("patience requires beam_size to be given")
     repetition.check_controls(options.repetition_penalty, options.no_repeat_ngram_size)
+    biasing.check_options(options.hotwords, options.hotword_bias, options.hotword_start_bias, options.sequence_bias)
 
 
 def candidate_mode(options: DecodingOptions, fallback_best_of: Optional[int], temperature: float) -> Tuple[str, int]:
@@ -260,6 +271,13 @@ class WhisperDecoding(HostLoops, DeviceLoop):
             self.logit_filters.append(RepetitionPenalty(self.options.repetition_penalty, self.tokenizer.eot, self.sample_begin))
         if self.options.no_repeat_ngram_size != 0:
             self.logit_filters.append(NoRepeatNGram(self.options.no_repeat_ngram_size, self.tokenizer.eot, self.sample_begin))
+        # hotwords / sequence bias (biasing.py): one table per instance, built once; directly behind the repetition filters of the literal
+        # loops and one launch behind wm_repeat_controls in the device loop (_Group._token_step) -- with the defaults neither exists
+        self.bias_on = biasing.bias_on(self.options.hotwords, self.options.sequence_bias)
+        self.bias_table = self._build_bias_table(self.options.hotwords, self.options.sequence_bias) if self.bias_on else None
+        self._bias_dev = None             # (items, pool, count): device buffers of fixed capacity, allocated by the first device-loop call
+        if self.bias_on:
+            self.logit_filters.append(SequenceBias(self.bias_table, self.tokenizer.eot, self.sample_begin))
         self.max_initial_timestamp_index = None
         if self.options.suppress_blank:
             self.logit_filters.append(SuppressBlank(self.tokenizer, self.sample_begin))
@@ -413,6 +431,45 @@ class WhisperDecoding(HostLoops, DeviceLoop):
         if not prompts or any(t < 0 or t >= V for p in prompts for t in p):
             raise ValueError("set_prompts: need one list of token ids of the vocabulary per utterance")
         self._prompts = prompts
+
+    # ---- hotwords / sequence bias ------------------------------------------------------------------------
+    def _build_bias_table(self, hotwords, sequence_bias, hotword_bias=None, hotword_start_bias=None) -> "biasing.Table":
+        o = self.options
+        return biasing.build_table(hotwords, sequence_bias, o.hotword_bias if hotword_bias is None else hotword_bias,
+                                   o.hotword_start_bias if hotword_start_bias is None else hotword_start_bias,
+                                   eot=self.tokenizer.eot, tokenizer=self.tokenizer)
+
+    def set_bias(self, hotwords=None, sequence_bias=None, hotword_bias: Optional[float] = None,
+                 hotword_start_bias: Optional[float] = None) -> None:
+        """Another table for the next main_loop calls -- a per-file vocabulary -- on an instance that was BUILT with a bias (its token
+        steps and captured graphs contain the launch; an instance built without one has no launch to feed and refuses).  The table
+        replaces the old one whole (neither option given: an empty table, nothing is biased); the biases default to the options'.  The
+        device buffers have a fixed capacity and are rewritten in place on the current stream: no graph is rebuilt, a replayed step
+        reads the new items and their number from device memory.  Call it between main_loop calls."""
+        if not self.bias_on:
+            raise ValueError("set_bias: needs an instance built with hotwords / sequence_bias (the token step of any other has no bias launch)")
+        table = self._build_bias_table(hotwords, sequence_bias, hotword_bias, hotword_start_bias)
+        self.bias_table = table
+        for f in self.logit_filters:
+            if isinstance(f, SequenceBias):
+                f.table = table
+        if self._bias_dev is not None:
+            self._upload_bias(self._bias_dev[0].device)
+
+    def _upload_bias(self, device):
+        """The table in the instance's device buffers (allocated once, at the table's bounds), on the current stream."""
+        if self._bias_dev is None:
+            self._bias_dev = (torch.zeros(4 * biasing.MAX_ITEMS, dtype=torch.int32, device=device),
+                              torch.zeros(biasing.MAX_POOL, dtype=torch.int32, device=device),
+                              torch.zeros(1, dtype=torch.int32, device=device))
+        items, pool, count = self._bias_dev
+        t = self.bias_table
+        if len(t):
+            items[:4 * len(t)].copy_(torch.from_numpy(t.packed.view(np.int32).reshape(-1).copy()))
+        if t.pool.size:
+            pool[:t.pool.size].copy_(torch.from_numpy(t.pool.copy()))
+        count.copy_(torch.tensor([len(t)], dtype=torch.int32))          # (items beyond it are stale and never read)
+        return self._bias_dev
 
     def _initial_token_rows(self, n_audio, device):
         tokens = self.tokens if self.tokens.shape[0] == n_audio else self._start_rows(n_audio)

@@ -173,11 +173,13 @@ class _Group:
                                               live_groups=self.live_groups, **counted)
 
     def _token_step(self, logits_ptr, row_stride, cur_len, n_past_dev=None) -> None:
-        """What follows a group's decoder launch: the repetition controls where one is on, then the fused greedy step, or the beam
-        step and the cache reorder."""
+        """What follows a group's decoder launch: the repetition controls where one is on, the hotword / sequence bias of an instance
+        built with one, then the fused greedy step, or the beam step and the cache reorder."""
         dec, call = self.dec, self.call
         if dec.repeat_controls_on:
             dec._repeat_controls(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, n_past_dev=n_past_dev)
+        if dec.bias_on:
+            dec._sequence_bias(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, n_past_dev=n_past_dev)
         if call.beam:
             dec._beam(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, self.kv_table, call.ignore_eot, n_past_dev=n_past_dev)
         else:
@@ -548,7 +550,7 @@ class DeviceLoop:
         return live
 
     def _fill_rows(self, io, st, lo, hi, logits_ptr, row_stride, cur_len, n_past_dev) -> None:
-        """The fields wm_greedy_io, wm_beam_io and wm_repeat_io share: where rows [lo, hi) of the batch state `st` are -- their logits,
+        """The fields wm_greedy_io, wm_beam_io, wm_repeat_io and wm_bias_io share: where rows [lo, hi) of the batch state `st` are -- their logits,
         tokens and `done` flags -- and how long they are (`cur_len`, or the device step counter of a captured step)."""
         io.logits, io.row_stride = logits_ptr, row_stride
         io.batch, io.n_vocab = hi - lo, self.decoder_config['vocab_size']
@@ -579,6 +581,17 @@ class DeviceLoop:
         io.sample_begin, io.eot = self.sample_begin, self.tokenizer.eot
         io.repetition_penalty, io.no_repeat_ngram_size = float(self.options.repetition_penalty), int(self.options.no_repeat_ngram_size)
         native.check(native.load_library().wm_repeat_controls(C.byref(io), stream), "wm_repeat_controls")
+
+    def _sequence_bias(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None):
+        """Hotwords / sequence bias (wm_sequence_bias, csrc/bias.hip) on the raw logits of rows [lo, hi) of the batch state `st`, behind
+        the repetition controls and before the token step: the instance's table, its item count read on the device."""
+        items, pool, count = self._bias_dev
+        io = native.WmBiasIO()
+        self._fill_rows(io, st, lo, hi, logits_ptr, row_stride, cur_len, n_past_dev)
+        io.sample_begin, io.eot = self.sample_begin, self.tokenizer.eot
+        io.items, io.pool, io.n_items_dev = items.data_ptr(), pool.data_ptr(), count.data_ptr()
+        io.capacity, io.pool_capacity = items.numel() // 4, pool.numel()
+        native.check(native.load_library().wm_sequence_bias(C.byref(io), stream), "wm_sequence_bias")
 
     def _greedy(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, n_past_dev=None, temperature=None):
         """Fused logit rules + arg-max + append for utterances [lo, hi) of the batch state `st`."""
@@ -661,6 +674,8 @@ class DeviceLoop:
         st = self._fast_state(n_batch, dev)
         one_row = self._may_run_alone(bounds, n_micro, self.groups_sequential, "found before the decode loop", peek=not _retry)
         cross = self._reset_state(st, audio_features, tokens0, row_limit, n_cand, reseed=temp != 0 and not _retry)
+        if self.bias_on and self._bias_dev is None:
+            self._upload_bias(dev)        # (the first device-loop call: on this stream, before the groups' streams fork from it)
         if self.cu_partition and n_micro > 1 and self.decoder_session.qkv_amax is None and row_limit is None and temp == self.options.temperature:
             return self._main_loop_partitioned(audio_features, st, cross, L0, n_micro, bounds, ignore_eot)
         # 3. group construction
@@ -707,6 +722,9 @@ class DeviceLoop:
             return
         if self.repeat_controls_on:
             raise ValueError("repetition_penalty / no_repeat_ngram_size are not supported by the CU-partitioned schedule (cu_partition = True): "
+                             "it has a loop of its own; use the default loop")
+        if self.bias_on:
+            raise ValueError("hotwords / sequence_bias are not supported by the CU-partitioned schedule (cu_partition = True): "
                              "it has a loop of its own; use the default loop")
         if n_micro > 1 and self.beam:
             raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")

@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 
+import biasing
 import timing
 from session import TensorInfo, str_dtype_to_trt, trt_dtype_to_torch, logger
 from tokenizer import Tokenizer
@@ -150,6 +151,28 @@ class NoRepeatNGram(LogitFilter):
             match &= sampled[:, k: k + m - n + 1] == sampled[:, m - n + 1 + k, None]
         rows, cols = (match & (nxt >= 0) & (nxt < self.eot)).nonzero(as_tuple=True)
         logits[rows, nxt[rows, cols]] = -np.inf
+
+
+class SequenceBias(LogitFilter):
+    """Hotwords and sequence bias of biasing.py in torch: per row and text token, the matching item of the table with the greatest
+    prefix adds its bias -- once, in fp32, rounded to fp16; biases are never summed.  Placed directly behind the two repetition
+    filters.  The match and the sum run on the host whatever device the logits live on, as RepetitionPenalty's arithmetic does.
+    `table` (a biasing.Table) may be replaced between calls (WhisperDecoding.set_bias)."""
+
+    def __init__(self, table, eot: int, sample_begin: int):
+        self.table, self.eot, self.sample_begin = table, eot, sample_begin
+
+    def apply(self, logits: Tensor, tokens: Tensor):
+        rows, ids, bias = [], [], []
+        for b, h in enumerate(tokens[:, self.sample_begin:].cpu().tolist()):
+            for t, v in biasing.winners(self.table.items, h).items():
+                if 0 <= t < self.eot:
+                    rows.append(b), ids.append(t), bias.append(v)
+        if not rows:
+            return
+        x = logits[rows, ids].float().cpu()                      # one winner per (row, token): every logit is read and written once
+        y = (x + torch.tensor(bias, dtype=torch.float32)).to(logits.dtype)
+        logits[rows, ids] = y.to(logits.device)
 
 
 class GreedyDecoder:

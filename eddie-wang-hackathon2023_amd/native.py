@@ -91,6 +91,7 @@ EXPORTS = (
     "wm_decoder_prefill_workspace_bytes", "wm_decoder_prefill", "wm_attn_prefill_self", "wm_attn_prefill_cross",
     "wm_repeat_controls",
     "wm_attn_encoder_ex",
+    "wm_sequence_bias",
 )
 
 
@@ -208,6 +209,22 @@ class WmRepeatIO(C.Structure):
         ("repetition_penalty", C.c_float),
         ("no_repeat_ngram_size", C.c_int32),
         ("done", C.c_void_p),
+    ]
+
+
+class WmBiasIO(C.Structure):
+    """wm_bias_io (include/whisper_mi355.h): hotwords and sequence bias on the raw logits of a token step."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("row_stride", C.c_int64),
+        ("batch", C.c_int32), ("n_vocab", C.c_int32),
+        ("tokens", C.c_void_p), ("tokens_ld", C.c_int32),
+        ("cur_len", C.c_int32),
+        ("n_past_dev", C.c_void_p),
+        ("sample_begin", C.c_int32), ("eot", C.c_int32),
+        ("done", C.c_void_p),
+        ("items", C.c_void_p), ("pool", C.c_void_p),
+        ("capacity", C.c_int32), ("pool_capacity", C.c_int32),
+        ("n_items_dev", C.c_void_p),
     ]
 
 
@@ -419,6 +436,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_flac_info.argtypes = [vp, sz, C.POINTER(WmFlacStreamInfo)]
     lib.wm_flac_decode.argtypes = [vp, sz, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.wm_repeat_controls.argtypes = [C.POINTER(WmRepeatIO), vp]
+    lib.wm_sequence_bias.argtypes = [C.POINTER(WmBiasIO), vp]
     lib.wm_step_advance.argtypes = [vp, vp]
     lib.wm_step_finish.argtypes = [vp, vp, i32, vp, vp]
     lib.wm_beam_workspace_bytes.argtypes = [i32, i32]

@@ -21,6 +21,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+import biasing
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 from normalizers import EnglishTextNormalizer
@@ -350,12 +351,14 @@ def parse_arguments(argv=None):
                         help="beam search: the beams of an utterance read one copy of its cross-attention K/V (off by default)")
     parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
     parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
+    biasing.add_arguments(parser)
     return parser.parse_args(argv)
 
 
 def decoding_options(args) -> DecodingOptions:
     return DecodingOptions(beam_size=args.beam_size, patience=args.patience, repetition_penalty=args.repetition_penalty,
-                           no_repeat_ngram_size=args.no_repeat_ngram_size)
+                           no_repeat_ngram_size=args.no_repeat_ngram_size,
+                           **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file))
 
 
 if __name__ == '__main__':

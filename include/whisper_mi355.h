@@ -71,7 +71,8 @@ typedef struct wm_dims {
  *      (still 8: entries and a struct of their own, no existing struct or signature changed) wm_decoder_prefill / wm_prefill_io,
  *      wm_decoder_prefill_workspace_bytes; test-only entries wm_attn_prefill_self, wm_attn_prefill_cross
  *      (still 8: an entry and a struct of its own) wm_repeat_controls / wm_repeat_io
- *      (still 8: a test-only entry and a struct of its own) wm_attn_encoder_ex / wm_attn_encoder_io */
+ *      (still 8: a test-only entry and a struct of its own) wm_attn_encoder_ex / wm_attn_encoder_io
+ *      (still 8: an entry and structs of its own) wm_sequence_bias / wm_bias_io / wm_bias_item */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -331,6 +332,47 @@ typedef struct wm_repeat_io {
     const int32_t* done;                      /* optional int32 [batch]: a row whose flag is set is left untouched */
 } wm_repeat_io;
 int wm_repeat_controls(const wm_repeat_io* io, wm_stream_t stream);
+
+/* ---- hotwords and sequence bias (added within ABI 8: an entry and structs of its own) ----------------------------------
+ * A bias on the raw logits of a token step, in place, AFTER wm_repeat_controls and BEFORE the logit filters of wm_greedy_step /
+ * wm_beam_step: one launch inside the step (biasing.py states the contract on the host and builds the table).
+ * The table: `items` (wm_bias_item: target, k, offset, bias) and `pool` (int32 tokens); item i reads "if the last k tokens of H
+ * equal pool[offset .. offset + k - 1] (k = 0 always matches, also on an empty H), token `target` gets `bias`".  H is the history of
+ * wm_repeat_io: tokens[b][sample_begin .. cur_len - 1], timestamps included.  Per row and target, among the matching items the one
+ * with the greatest k wins (equal k: the earlier item), and exactly ONE update is applied: x = fp32(logits[target]); y = x + bias,
+ * one correctly rounded fp32 addition; logits[target] = fp16(y), round to nearest even.  -inf stays -inf; biases are never summed.
+ * The table must be sorted by (target ascending, k descending), as biasing.build_table leaves it: every logit is then read and
+ * written by exactly one thread.  The results on an unsorted table are unspecified; on ANY table and whatever the device words hold
+ * the kernel stays inside its arrays: items beyond `capacity`, a k outside [0, WM_BIAS_MAX_K] or above the row's history, a prefix
+ * that leaves [0, pool_capacity) and a target outside [0, eot) make an item inert.
+ * The number of items a launch sees is min(*n_items_dev, capacity) (all `capacity` items without the word), read on the device:
+ * a captured launch follows a table rewritten in place.  capacity = 0: nothing is launched.
+ * Refused (rc 1, nothing launched): the null / range / alignment refusals of wm_repeat_controls (its history bound included); a null
+ * `items` or `pool` with capacity > 0; capacity outside [0, WM_BIAS_MAX_ITEMS]; pool_capacity outside [0, WM_BIAS_MAX_POOL]; `items`
+ * not 16-byte aligned, `pool` / `n_items_dev` not 4-byte aligned.  Asynchronous on `stream`, no allocation, capturable. */
+#define WM_BIAS_MAX_ITEMS 4096
+#define WM_BIAS_MAX_POOL 4096
+#define WM_BIAS_MAX_K 31                    /* a phrase has at most 32 tokens */
+typedef struct wm_bias_item {
+    int32_t target;                           /* the text token that gets `bias` */
+    int32_t k;                                /* tokens of the prefix */
+    int32_t offset;                           /* where the prefix starts in the pool */
+    float bias;
+} wm_bias_item;
+typedef struct wm_bias_io {
+    void* logits; int64_t row_stride;         /* as wm_repeat_io: fp16, the LAST position's rows, any 2-byte address */
+    int32_t batch, n_vocab;
+    const int32_t* tokens; int32_t tokens_ld;
+    int32_t cur_len;
+    const int32_t* n_past_dev;                /* optional device step counter: cur_len = *n_past_dev + 1 */
+    int32_t sample_begin, eot;
+    const int32_t* done;                      /* optional int32 [batch]: a row whose flag is set is left untouched */
+    const wm_bias_item* items;                /* device, [capacity], 16-byte aligned */
+    const int32_t* pool;                      /* device, int32 [pool_capacity] */
+    int32_t capacity, pool_capacity;
+    const int32_t* n_items_dev;               /* optional device word: the items in use */
+} wm_bias_io;
+int wm_sequence_bias(const wm_bias_io* io, wm_stream_t stream);
 
 /* ---- beam search step (added within ABI 8: new entries only, no existing struct or signature changed) ----------------
  * The semantics of upstream Whisper's BeamSearchDecoder.update on the device, one call per token step of an utterance
