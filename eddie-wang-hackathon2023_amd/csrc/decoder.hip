@@ -874,8 +874,7 @@ int wm_profile_read(double* total_ms, int64_t* count, int reset) {
 }
 
 // ================================================================================================ greedy
-int wm_greedy_step(const wm_greedy_io* io, wm_stream_t stream) {
-    WM_REQUIRE(io && io->logits && io->tokens && io->sum_logprobs, "wm_greedy_step: null argument");
+static GreedyParams greedy_params(const wm_greedy_io* io) {
     GreedyParams p{};
     p.logits = (h16*)io->logits; p.ld_row = io->row_stride; p.B = io->batch; p.V = io->n_vocab;
     p.tokens = io->tokens; p.ld_tok = io->tokens_ld; p.cur_len = io->cur_len; p.sum_logprobs = io->sum_logprobs;
@@ -884,10 +883,31 @@ int wm_greedy_step(const wm_greedy_io* io, wm_stream_t stream) {
     p.max_initial_ts = io->max_initial_timestamp_index; p.apply_rules = io->apply_rules; p.n_done = io->n_done;
     p.t_dev = io->n_past_dev;
     p.done = io->done; p.row_limit = io->row_limit;
-    WM_REQUIRE(io->temperature >= 0.f, "wm_greedy_step: negative temperature");
     p.temperature = io->temperature; p.seed_lo = (uint32_t)io->seed; p.seed_hi = (uint32_t)(io->seed >> 32);
     p.seed_dev = io->seed_dev; p.row0 = io->row0;
-    return launch_greedy(p, (hipStream_t)stream);
+    return p;
+}
+
+int wm_greedy_step(const wm_greedy_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io && io->logits && io->tokens && io->sum_logprobs, "wm_greedy_step: null argument");
+    WM_REQUIRE(io->temperature >= 0.f, "wm_greedy_step: negative temperature");
+    return launch_greedy(greedy_params(io), (hipStream_t)stream);
+}
+
+// ================================================================================================ truncated sampling
+int wm_sample_step(const wm_sample_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io && io->g.logits && io->g.tokens && io->g.sum_logprobs, "wm_sample_step: null argument");
+    WM_REQUIRE(io->g.batch >= 1 && io->g.n_vocab >= 1, "wm_sample_step: batch %d or n_vocab %d below 1", io->g.batch, io->g.n_vocab);
+    WM_REQUIRE(io->g.temperature > 0.f && std::isfinite(io->g.temperature), "wm_sample_step: temperature must be finite and > 0 (wm_greedy_step takes the arg-max)");
+    WM_REQUIRE(io->top_k >= 0, "wm_sample_step: top_k %d is negative", io->top_k);
+    WM_REQUIRE(io->exp2_scale > 0.f && std::isfinite(io->exp2_scale), "wm_sample_step: exp2_scale must be log2(e) / temperature, finite and > 0");
+    WM_REQUIRE(io->top_p_q16 >= 1 && io->top_p_q16 <= 65536, "wm_sample_step: top_p_q16 %d outside [1, 65536]", io->top_p_q16);
+    WM_REQUIRE(io->min_p_gap <= 0.f, "wm_sample_step: min_p_gap must be temperature * ln(min_p) <= 0, or -inf");
+    SampleParams sp{};
+    sp.g = greedy_params(&io->g);
+    sp.top_k = io->top_k; sp.exp2_scale = io->exp2_scale; sp.top_p_q16 = io->top_p_q16; sp.min_p_gap = io->min_p_gap;
+    sp.cut_out = io->cut_out; sp.kept_out = io->kept_out;
+    return launch_sample(sp, (hipStream_t)stream);
 }
 
 int wm_step_advance(int32_t* counter, wm_stream_t stream) { return launch_step_advance(counter, (hipStream_t)stream); }

@@ -281,6 +281,16 @@ struct GreedyParams {
     int row0;                                // global index of row 0 (draws are keyed on the global row, not on the launch)
 };
 int launch_greedy(const GreedyParams& p, hipStream_t stream);
+// ---------------------------------------------------------------- truncate.hip
+struct SampleParams {
+    GreedyParams g;                          // the token step's own fields; temperature > 0
+    int top_k;                               // 0 = off
+    float exp2_scale;                        // c = fp32(log2(e) / temperature)
+    int top_p_q16;                           // P = round(p * 2^16), 65536 = off
+    float min_p_gap;                         // fp32(temperature * ln q), -inf = off
+    float* cut_out; int32_t* kept_out;       // optional [B]: the value of the last kept class, the number of kept tokens
+};
+int launch_sample(const SampleParams& p, hipStream_t stream);
 int launch_step_advance(int32_t* counter, hipStream_t stream);
 int launch_step_finish(int32_t* counter, const int32_t* done, int B, int32_t* live, hipStream_t stream);
 // ... and, for candidate groups of G rows (B % G == 0), the utterances with a live row: live_utt[0] = their number, then their indices, ascending

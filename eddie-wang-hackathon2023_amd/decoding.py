@@ -25,7 +25,11 @@ What differs underneath:
   `main_loop` -- only when one of them is on;
 * `hotwords` / `sequence_bias` (contextual biasing / Hugging Face; biasing.py states the contract and builds the table): `SequenceBias`
   directly behind the two repetition filters of the literal loops, wm_sequence_bias (csrc/bias.hip) behind wm_repeat_controls in the
-  token step of `main_loop` -- only on an instance built with a bias; `set_bias` rewrites the table between calls.
+  token step of `main_loop` -- only on an instance built with a bias; `set_bias` rewrites the table between calls;
+* `top_k` / `top_p` / `min_p` (Hugging Face / CTranslate2; truncation.py states the contract): above temperature 0 the draw is restricted to
+  a kept set -- `GreedyDecoder` masks its Categorical in the literal loops, wm_sample_step (csrc/truncate.hip) takes the place of
+  wm_greedy_step in the token step of `main_loop`, only for calls at temperature > 0 on an instance with one of them on.  At
+  temperature 0 and under beam search they are inert.
 
 This module holds the options, the results and `WhisperDecoding`'s construction and call contract (start rows, prompts, post_process).
 host_decoding.py holds the literal loops and the host filter / decoder classes and imports neither `native` nor `ctypes`;
@@ -47,6 +51,7 @@ from torch import Tensor
 
 import biasing
 import repetition
+import truncation
 from build import get_engine_name
 from device_loop import (DeviceLoop, call_key, fork, groups_run_alone, join, language_key, partition_key,  # noqa: F401 (re-exported)
                          prefill_key, step_key, steps_side_by_side)
@@ -84,6 +89,11 @@ class DecodingOptions:
     hotword_bias: float = 3.0           # added to the token that continues a hotword (a parameter, not a measurement)
     hotword_start_bias: float = 1.5     # added to the first token of a hotword, at every step
     sequence_bias: Optional[Tuple[Tuple[Tuple[int, ...], float], ...]] = None   # ((token tuple, bias), ...): the token that completes a sequence
+    # truncated sampling (truncation.py states the contract): which tokens a draw at temperature > 0 may take, decided on the distribution
+    # AFTER Whisper's own rules; the booked log-probability stays that of the untruncated distribution.  Inert at temperature 0 / beam search
+    top_k: int = 0                      # >= 0; only the k most likely tokens (ties at the k-th value are kept); 0 = off
+    top_p: float = 1.0                  # (0, 1]; the smallest set of most likely tokens whose mass reaches p; 1.0 = off
+    min_p: float = 0.0                  # [0, 1); tokens less likely than min_p times the most likely one are dropped; 0.0 = off
 
 
 @dataclass(frozen=True)
@@ -115,6 +125,7 @@ def check_decoding_options(options: DecodingOptions) -> None:
         raise ValueError("patience requires beam_size to be given")
     repetition.check_controls(options.repetition_penalty, options.no_repeat_ngram_size)
     biasing.check_options(options.hotwords, options.hotword_bias, options.hotword_start_bias, options.sequence_bias)
+    truncation.check_options(options.top_k, options.top_p, options.min_p)
 
 
 def candidate_mode(options: DecodingOptions, fallback_best_of: Optional[int], temperature: float) -> Tuple[str, int]:
@@ -278,6 +289,10 @@ class WhisperDecoding(HostLoops, DeviceLoop):
         self._bias_dev = None             # (items, pool, count): device buffers of fixed capacity, allocated by the first device-loop call
         if self.bias_on:
             self.logit_filters.append(SequenceBias(self.bias_table, self.tokenizer.eot, self.sample_begin))
+        # top-k / top-p / min-p (truncation.py): no filter -- the kept set is decided AFTER the rules, inside the sampler: GreedyDecoder masks
+        # its draw in the literal loops, wm_sample_step takes wm_greedy_step's place in the device loop (_Group._token_step) for calls
+        # at temperature > 0 -- with the defaults neither changes
+        self.truncation_on = truncation.truncation_on(self.options.top_k, self.options.top_p, self.options.min_p)
         self.max_initial_timestamp_index = None
         if self.options.suppress_blank:
             self.logit_filters.append(SuppressBlank(self.tokenizer, self.sample_begin))
@@ -293,7 +308,7 @@ class WhisperDecoding(HostLoops, DeviceLoop):
         if self.options.beam_size is not None:
             self.decoder = BeamSearchDecoder(self.options.beam_size, self.tokenizer.eot, self.sample_begin, self.options.patience)
         else:
-            self.decoder = GreedyDecoder(self.options.temperature, self.tokenizer.eot)
+            self.decoder = GreedyDecoder(self.options.temperature, self.tokenizer.eot, self._truncation())
         self.beam = self.options.beam_size is not None     # (beam_size = 1 is beam search too: one beam, a pool of finished candidates)
 
     def _init_schedule(self) -> None:
@@ -492,8 +507,13 @@ class WhisperDecoding(HostLoops, DeviceLoop):
         t = float(self.options.temperature if temperature is None else temperature)
         mode, n_cand = candidate_mode(self.options, self.fallback_best_of, t)
         if self.beam and mode == "sample":
-            return GreedyDecoder(t, self.tokenizer.eot), n_cand
+            return GreedyDecoder(t, self.tokenizer.eot, self._truncation()), n_cand
         return self.decoder, self.n_group
+
+    def _truncation(self) -> Optional[Tuple[int, float, float]]:
+        """(top_k, top_p, min_p) of an instance with one of them on, else None: what the samplers of the literal loops take."""
+        o = self.options
+        return (int(o.top_k), float(o.top_p), float(o.min_p)) if self.truncation_on else None
 
     def compression_ratio(self, text) -> float:
         text_bytes = text.encode("utf-8")

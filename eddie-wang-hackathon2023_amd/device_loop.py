@@ -17,6 +17,7 @@ from torch import Tensor
 
 import native
 import timing
+import truncation
 from host_decoding import CHUNK_LENGTH, SuppressTokens
 from session import logger
 
@@ -174,7 +175,8 @@ class _Group:
 
     def _token_step(self, logits_ptr, row_stride, cur_len, n_past_dev=None) -> None:
         """What follows a group's decoder launch: the repetition controls where one is on, the hotword / sequence bias of an instance
-        built with one, then the fused greedy step, or the beam step and the cache reorder."""
+        built with one, then the fused greedy step -- the truncated sampling step in its place for a call at temperature > 0 on an
+        instance with top_k / top_p / min_p on -- or the beam step and the cache reorder."""
         dec, call = self.dec, self.call
         if dec.repeat_controls_on:
             dec._repeat_controls(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, n_past_dev=n_past_dev)
@@ -182,6 +184,8 @@ class _Group:
             dec._sequence_bias(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, n_past_dev=n_past_dev)
         if call.beam:
             dec._beam(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, self.kv_table, call.ignore_eot, n_past_dev=n_past_dev)
+        elif call.temperature > 0 and dec.truncation_on:
+            dec._sample(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, call.temperature, n_past_dev=n_past_dev)
         else:
             dec._greedy(call.st, self.lo, self.hi, logits_ptr, row_stride, cur_len, self.sm, n_past_dev=n_past_dev, temperature=call.temperature)
 
@@ -603,6 +607,17 @@ class DeviceLoop:
         io.row0, io.seed_dev = lo, st['seed'].data_ptr()
         native.check(native.load_library().wm_greedy_step(C.byref(io), stream), "wm_greedy_step")
 
+    def _sample(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, temperature, n_past_dev=None):
+        """The token step with the draw restricted by top_k / top_p / min_p (wm_sample_step, csrc/truncate.hip) for rows [lo, hi) of the
+        batch state `st`: `_greedy`'s fields and the scalars of truncation.params, baked into a captured step like the temperature."""
+        io = native.WmSampleIO()
+        self._fill_rules(io.g, st, lo, hi, logits_ptr, row_stride, cur_len, n_past_dev)
+        io.g.temperature = float(temperature)
+        io.g.row0, io.g.seed_dev = lo, st['seed'].data_ptr()
+        c, p_q16, gap = truncation.params(temperature, self.options.top_p, self.options.min_p)
+        io.top_k, io.exp2_scale, io.top_p_q16, io.min_p_gap = int(self.options.top_k), float(c), int(p_q16), float(gap)
+        native.check(native.load_library().wm_sample_step(C.byref(io), stream), "wm_sample_step")
+
     def _beam(self, st, lo, hi, logits_ptr, row_stride, cur_len, stream, kv_table, ignore_eot, n_past_dev=None):
         """Beam step + cache reorder for rows [lo, hi) (whole utterances) of the batch state `st`: wm_beam_step applies the logit rules,
         picks and moves the beams, wm_kv_reorder lets every layer's self-attention cache rows follow their parents."""
@@ -725,6 +740,9 @@ class DeviceLoop:
                              "it has a loop of its own; use the default loop")
         if self.bias_on:
             raise ValueError("hotwords / sequence_bias are not supported by the CU-partitioned schedule (cu_partition = True): "
+                             "it has a loop of its own; use the default loop")
+        if self.truncation_on:
+            raise ValueError("top_k / top_p / min_p are not supported by the CU-partitioned schedule (cu_partition = True): "
                              "it has a loop of its own; use the default loop")
         if n_micro > 1 and self.beam:
             raise ValueError("beam_size is not supported by the CU-partitioned schedule (cu_partition = True): use the default loop")

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 import biasing
+import truncation
 import timing
 from session import TensorInfo, str_dtype_to_trt, trt_dtype_to_torch, logger
 from tokenizer import Tokenizer
@@ -176,14 +177,21 @@ class SequenceBias(LogitFilter):
 
 
 class GreedyDecoder:
-    def __init__(self, temperature: float, eot: int):
-        self.temperature, self.eot = temperature, eot
+    """`kept` (optional, (top_k, top_p, min_p) with one of them on): above temperature 0 the draw is restricted to the kept set of
+    truncation.py, decided on the logits as the filters left them; the log-probability booked stays that of the unmasked logits."""
+
+    def __init__(self, temperature: float, eot: int, kept: Optional[Tuple[int, float, float]] = None):
+        self.temperature, self.eot, self.kept = temperature, eot, kept
 
     def update(self, tokens: Tensor, logits: Tensor, sum_logprobs: Tensor) -> Tuple[Tensor, bool]:
         if self.temperature == 0:
             next_tokens = logits.argmax(dim=-1)
-        else:
+        elif self.kept is None:
             next_tokens = torch.distributions.Categorical(logits=logits / self.temperature).sample()
+        else:
+            keep = truncation.keep_mask(logits.detach().float().cpu().numpy(), self.temperature, *self.kept)
+            masked = (logits / self.temperature).masked_fill(~torch.from_numpy(keep).to(logits.device), -np.inf)
+            next_tokens = torch.distributions.Categorical(logits=masked).sample()
         logprobs = F.log_softmax(logits.float(), dim=-1)
         current = logprobs[torch.arange(logprobs.shape[0]), next_tokens]
         alive = tokens[:, -1] != self.eot

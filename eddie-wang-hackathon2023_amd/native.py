@@ -92,6 +92,7 @@ EXPORTS = (
     "wm_repeat_controls",
     "wm_attn_encoder_ex",
     "wm_sequence_bias",
+    "wm_sample_step",
 )
 
 
@@ -225,6 +226,15 @@ class WmBiasIO(C.Structure):
         ("items", C.c_void_p), ("pool", C.c_void_p),
         ("capacity", C.c_int32), ("pool_capacity", C.c_int32),
         ("n_items_dev", C.c_void_p),
+    ]
+
+
+class WmSampleIO(C.Structure):
+    """wm_sample_io (include/whisper_mi355.h): a sampled token step with the draw restricted by top-k / top-p / min-p."""
+    _fields_ = [
+        ("g", WmGreedyIO),
+        ("top_k", C.c_int32), ("exp2_scale", C.c_float), ("top_p_q16", C.c_int32), ("min_p_gap", C.c_float),
+        ("cut_out", C.c_void_p), ("kept_out", C.c_void_p),
     ]
 
 
@@ -437,6 +447,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_flac_decode.argtypes = [vp, sz, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.wm_repeat_controls.argtypes = [C.POINTER(WmRepeatIO), vp]
     lib.wm_sequence_bias.argtypes = [C.POINTER(WmBiasIO), vp]
+    lib.wm_sample_step.argtypes = [C.POINTER(WmSampleIO), vp]
     lib.wm_step_advance.argtypes = [vp, vp]
     lib.wm_step_finish.argtypes = [vp, vp, i32, vp, vp]
     lib.wm_beam_workspace_bytes.argtypes = [i32, i32]

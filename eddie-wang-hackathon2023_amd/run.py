@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 import biasing
+import truncation
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 
@@ -41,13 +42,15 @@ def parse_arguments(argv=None):
     parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
     parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
     biasing.add_arguments(parser)
+    truncation.add_arguments(parser)
     return parser.parse_args(argv)
 
 
 def decoding_options(args) -> DecodingOptions:
     return DecodingOptions(beam_size=args.beam_size, patience=args.patience, repetition_penalty=args.repetition_penalty,
                            no_repeat_ngram_size=args.no_repeat_ngram_size,
-                           **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file))
+                           **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file),
+                           **truncation.options_from_args(args.top_k, args.top_p, args.min_p))
 
 
 def load_mel(input_file: str) -> torch.Tensor:
@@ -75,7 +78,7 @@ def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', inpu
              vocab: str = None, beam_size: int = None, patience: float = None, word_timestamps: bool = False,
              shared_cross_kv: bool = False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              hotwords: str = None, hotword_bias: float = biasing.HOTWORD_BIAS, hotword_start_bias: float = biasing.HOTWORD_START_BIAS,
-             sequence_bias_file: str = None):
+             sequence_bias_file: str = None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
     logging.basicConfig(level=getattr(logging, log_level.upper(), logging.ERROR))
     torch.cuda.set_device(0)
     mel = load_mel(input_file).to('cuda').type(torch.float16).unsqueeze(0)
@@ -83,7 +86,8 @@ def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', inpu
     whisper_encoding = WhisperEncoding(engine_dir)
     options = DecodingOptions(beam_size=beam_size, patience=patience, repetition_penalty=repetition_penalty,
                               no_repeat_ngram_size=no_repeat_ngram_size,
-                              **biasing.options_from_args(hotwords, hotword_bias, hotword_start_bias, sequence_bias_file))
+                              **biasing.options_from_args(hotwords, hotword_bias, hotword_start_bias, sequence_bias_file),
+                              **truncation.options_from_args(top_k, top_p, min_p))
     whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=options, shared_cross_kv=shared_cross_kv)
     begin_time = time.time()
     audio_features = whisper_encoding.get_audio_features(mel)

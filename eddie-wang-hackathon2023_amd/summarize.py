@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 import biasing
+import truncation
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 from normalizers import EnglishTextNormalizer
@@ -352,13 +353,15 @@ def parse_arguments(argv=None):
     parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
     parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
     biasing.add_arguments(parser)
+    truncation.add_arguments(parser)
     return parser.parse_args(argv)
 
 
 def decoding_options(args) -> DecodingOptions:
     return DecodingOptions(beam_size=args.beam_size, patience=args.patience, repetition_penalty=args.repetition_penalty,
                            no_repeat_ngram_size=args.no_repeat_ngram_size,
-                           **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file))
+                           **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file),
+                           **truncation.options_from_args(args.top_k, args.top_p, args.min_p))
 
 
 if __name__ == '__main__':

@@ -69,6 +69,7 @@ import numpy as np
 import torch
 
 import biasing
+import truncation
 import longform
 import native
 import sections as sections_mod
@@ -542,16 +543,18 @@ def parse_arguments(argv=None):
     parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
     parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
     biasing.add_arguments(parser)
+    truncation.add_arguments(parser)
     return parser.parse_args(argv)
 
 
 def build_decoding(args, engine_dir, prompted: bool) -> WhisperDecoding:
     """The WhisperDecoding of the command line: greedy as ever; --beam_size: beam search at 0 and --best_of samples above on one
     shared copy of the cross K/V; --best_of alone: best_of samples at the one temperature given.  --repetition_penalty /
-    --no_repeat_ngram_size and --hotwords / --sequence_bias_file go into the instance's options: every window, temperature and section
+    --no_repeat_ngram_size, --hotwords / --sequence_bias_file and --top_k / --top_p / --min_p go into the instance's options: every window, temperature and section
     decodes through it."""
     repeat = dict(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
-                  **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file))
+                  **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file),
+                  **truncation.options_from_args(args.top_k, args.top_p, args.min_p))
     if args.beam_size is not None:
         options = DecodingOptions(language=args.language, beam_size=args.beam_size, patience=args.patience, **repeat)
         return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,

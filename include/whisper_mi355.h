@@ -72,7 +72,8 @@ typedef struct wm_dims {
  *      wm_decoder_prefill_workspace_bytes; test-only entries wm_attn_prefill_self, wm_attn_prefill_cross
  *      (still 8: an entry and a struct of its own) wm_repeat_controls / wm_repeat_io
  *      (still 8: a test-only entry and a struct of its own) wm_attn_encoder_ex / wm_attn_encoder_io
- *      (still 8: an entry and structs of its own) wm_sequence_bias / wm_bias_io / wm_bias_item */
+ *      (still 8: an entry and structs of its own) wm_sequence_bias / wm_bias_io / wm_bias_item
+ *      (still 8: an entry and a struct of its own) wm_sample_step / wm_sample_io */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -373,6 +374,39 @@ typedef struct wm_bias_io {
     const int32_t* n_items_dev;               /* optional device word: the items in use */
 } wm_bias_io;
 int wm_sequence_bias(const wm_bias_io* io, wm_stream_t stream);
+
+/* ---- top-k / top-p / min-p sampling (added within ABI 8: an entry and a struct of its own) ----------------------------
+ * A WHOLE token step: wm_greedy_step at temperature > 0 with the draw restricted to a kept set (truncation.py states the contract
+ * on the host).  It takes the place of wm_greedy_step, it is not a launch in front of it: the kept set is a
+ * property of the distribution AFTER the step's own rules (suppress lists, timestamp rules, the text-versus-timestamp decision).
+ * Per row: A = the allowed tokens whose logit is not -inf, x_n their fp16 logits, m their maximum.  The values of A form classes
+ * v_1 = m > v_2 > ... with counts c_j; a class is kept or dropped whole, so the result is one number, the cut: token n may be
+ * drawn iff x_n >= cut.  Weights are integers: q(v) ~ 2^30 exp((v - m) / T) from d = fp32(v) - fp32(m), s = d * exp2_scale,
+ * i = rint(s), f = s - i, a degree-6 polynomial in f evaluated in single correctly rounded fp32 operations (no fused multiply-add),
+ * rounded to an integer and shifted right by -i with rounding; i < -31 weighs 0 (truncation.py: the coefficients and the
+ * measured error).  In Hugging Face's order:
+ *   top_k (0 = off)              j_k = the smallest j with c_1 + ... + c_j >= top_k: ties at the k-th value are all kept;
+ *   top_p_q16 = P (65536 = off)  with Q_j = sum_{i<=j} c_i q(v_i), Q = Q_{j_k}: j_p = the smallest j with Q_j * 2^16 >= P * Q;
+ *   min_p_gap (-inf = off)       classes with fp32(v) - fp32(m) >= min_p_gap are kept (the host passes fp32(T ln min_p)).
+ * The row keeps classes 1 .. min(j_k, j_p, j_q); class 1 always.  The draw is wm_greedy_step's Gumbel-max -- same generator, same
+ * coordinates (seed, row0 + b, position, token) -- over the kept tokens: with all three off every row draws exactly the token
+ * wm_greedy_step draws.  sum_logprobs books log_softmax over the UNTRUNCATED allowed set at temperature 1 and the logits row is
+ * not written apart from the suppress lists.  EOT stickiness, row_limit, done, n_done and the append are wm_greedy_step's.
+ * cut_out / kept_out (optional, [batch]): the value of the last kept class and the number of kept tokens (-inf and 0 for a row
+ * with nothing allowed), for tests.  The result of a row depends on the row alone.
+ * Refused (rc 1, nothing launched): what wm_greedy_step refuses; batch or n_vocab < 1; g.temperature <= 0 or not finite; top_k < 0;
+ * exp2_scale <= 0 or not finite; top_p_q16 outside [1, 65536]; min_p_gap > 0 or NaN.  Asynchronous on `stream`, no workspace, no
+ * allocation, capturable. */
+typedef struct wm_sample_io {
+    wm_greedy_io g;                           /* the token step; g.temperature = T > 0 */
+    int32_t top_k;                            /* 0: off */
+    float exp2_scale;                         /* c = fp32(log2(e) / T) */
+    int32_t top_p_q16;                        /* P = max(1, round(top_p * 2^16)); 65536: off */
+    float min_p_gap;                          /* fp32(T * ln(min_p)); -inf: off */
+    float* cut_out;                           /* optional fp32 [batch] */
+    int32_t* kept_out;                        /* optional int32 [batch] */
+} wm_sample_io;
+int wm_sample_step(const wm_sample_io* io, wm_stream_t stream);
 
 /* ---- beam search step (added within ABI 8: new entries only, no existing struct or signature changed) ----------------
  * The semantics of upstream Whisper's BeamSearchDecoder.update on the device, one call per token step of an utterance
