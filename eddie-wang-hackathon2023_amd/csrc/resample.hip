@@ -71,6 +71,42 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const V* __restric
     }
 }
 
+// The channel form (wm_resample_channels): the same tile, the same tap order and the same table, but the staging SELECTS channel
+// blockIdx.y instead of summing -- x_c[k] = fp32(v[k][c]) / 1 * scale, the expression the downmix has for a mono file -- and the
+// output is row c of out [channels][out_ld].  All channels in one launch: the interleaved input is read once per channel from L2
+// instead of being copied apart first.
+template <typename V>
+__global__ __launch_bounds__(RS_THREADS) void resample_channels_kernel(const V* __restrict__ pcm, int channels, long n_in, float scale,
+                                                                       const float* __restrict__ table, int L, int M, int half,
+                                                                       float* __restrict__ out, long out_ld, long n_out) {
+    extern __shared__ float xs[];
+    const int c = blockIdx.y;
+    const long n0 = (long)blockIdx.x * RS_TILE;
+    const long nm0 = n0 * (long)M;
+    const long q0 = nm0 / L;
+    const int p0 = (int)(nm0 - q0 * L);
+    const int r0 = (int)(n0 % L);
+    const int count = (int)(n_out - n0 < RS_TILE ? n_out - n0 : RS_TILE);
+    const int T = 2 * half + 1;
+    const int span = (p0 + (count - 1) * M) / L + T;       // at most the launcher's span_cap, as in resample_kernel
+    const long k0 = q0 - half;
+    for (int s = threadIdx.x; s < span; s += RS_THREADS) {
+        const long k = k0 + s;
+        xs[s] = (k >= 0 && k < n_in) ? rs_downmix(pcm + c, k * channels, 1, 1.0f, scale) : 0.f;
+    }
+    __syncthreads();
+    float* row = out + (long)c * out_ld;
+    for (int d = threadIdx.x; d < count; d += RS_THREADS) {
+        const int r = (r0 + d) % L;
+        const int base = (p0 + d * M) / L;
+        const float* h = table + r;
+        float acc = 0.f;
+#pragma unroll 4
+        for (int j = 0; j < T; ++j) acc = fmaf(xs[base + j], h[(long)j * L], acc);
+        row[n0 + d] = acc;
+    }
+}
+
 }  // namespace
 
 int launch_resample(const void* pcm, int dtype, int channels, long n_in, float scale, const float* table, int L, int M, int half,
@@ -96,6 +132,29 @@ int launch_resample(const void* pcm, int dtype, int channels, long n_in, float s
     return 0;
 }
 
+int launch_resample_channels(const void* pcm, int dtype, int channels, long n_in, float scale, const float* table, int L, int M,
+                             int half, float* out, long out_ld, long n_out, hipStream_t stream) {
+    const long T = 2L * half + 1;
+    const long span_cap = ((long)L - 1 + (long)(RS_TILE - 1) * M) / L + T;
+    WM_REQUIRE(span_cap <= RS_MAX_SPAN, "wm_resample_channels: L=%d M=%d half=%d need %ld floats of LDS per tile (at most %ld)", L, M,
+               half, span_cap, RS_MAX_SPAN);
+    const long grid = (n_out + RS_TILE - 1) / RS_TILE;
+    WM_REQUIRE(grid <= 0x7fffffffL, "wm_resample_channels: %ld outputs are more than one launch takes", n_out);
+    const size_t lds = (size_t)span_cap * sizeof(float);
+    const dim3 g((unsigned)grid, (unsigned)channels), b(RS_THREADS);
+    if (dtype == 0)
+        hipLaunchKernelGGL(resample_channels_kernel<float>, g, b, lds, stream, (const float*)pcm, channels, n_in, scale, table, L, M,
+                           half, out, out_ld, n_out);
+    else if (dtype == 1)
+        hipLaunchKernelGGL(resample_channels_kernel<int16_t>, g, b, lds, stream, (const int16_t*)pcm, channels, n_in, scale, table, L,
+                           M, half, out, out_ld, n_out);
+    else
+        hipLaunchKernelGGL(resample_channels_kernel<int32_t>, g, b, lds, stream, (const int32_t*)pcm, channels, n_in, scale, table, L,
+                           M, half, out, out_ld, n_out);
+    WM_LAUNCH_CHECK(stream, "resample_channels");
+    return 0;
+}
+
 }  // namespace wm
 
 using namespace wm;
@@ -112,4 +171,20 @@ extern "C" int wm_resample(const void* pcm, int dtype, int channels, int64_t n_i
     const int64_t want = (n_in * L + M - 1) / M;
     WM_REQUIRE(n_out == want, "wm_resample: n_out=%lld, ceil(n_in L / M) = %lld", (long long)n_out, (long long)want);
     return launch_resample(pcm, dtype, channels, (long)n_in, scale, table, L, M, half, out, (long)n_out, (hipStream_t)stream);
+}
+
+extern "C" int wm_resample_channels(const void* pcm, int dtype, int channels, int64_t n_in, float scale, const float* table, int L,
+                                    int M, int half, float* out, int64_t out_ld, int64_t n_out, wm_stream_t stream) {
+    WM_REQUIRE(pcm && table && out, "wm_resample_channels: null argument");
+    WM_REQUIRE(dtype >= 0 && dtype <= 2, "wm_resample_channels: dtype %d is not 0 (f32), 1 (i16) or 2 (i32)", dtype);
+    WM_REQUIRE(channels >= 1 && channels <= 8, "wm_resample_channels: %d channels (1..8)", channels);
+    WM_REQUIRE(L >= 1 && M >= 1 && half >= 1, "wm_resample_channels: L=%d M=%d half=%d must be >= 1", L, M, half);
+    WM_REQUIRE(L != M, "wm_resample_channels: L == M = %d is no rate change", L);
+    WM_REQUIRE(L <= (1 << 20) && M <= (1 << 20) && half <= (1 << 16), "wm_resample_channels: L=%d M=%d half=%d out of range", L, M, half);
+    WM_REQUIRE(n_in >= 1 && n_in <= (int64_t)1 << 40, "wm_resample_channels: n_in=%lld", (long long)n_in);
+    const int64_t want = (n_in * L + M - 1) / M;
+    WM_REQUIRE(n_out == want, "wm_resample_channels: n_out=%lld, ceil(n_in L / M) = %lld", (long long)n_out, (long long)want);
+    WM_REQUIRE(out_ld >= n_out, "wm_resample_channels: out_ld=%lld is below n_out=%lld", (long long)out_ld, (long long)n_out);
+    return launch_resample_channels(pcm, dtype, channels, (long)n_in, scale, table, L, M, half, out, (long)out_ld, (long)n_out,
+                                    (hipStream_t)stream);
 }

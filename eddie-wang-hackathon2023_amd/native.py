@@ -93,6 +93,7 @@ EXPORTS = (
     "wm_attn_encoder_ex",
     "wm_sequence_bias",
     "wm_sample_step",
+    "wm_resample_channels", "wm_channel_top_workspace_bytes", "wm_channel_top",
 )
 
 
@@ -467,6 +468,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_zero_pad_rows.argtypes = [vp, i32, i32, i32, vp]
     lib.wm_mel_windows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.wm_resample.argtypes = [vp, i32, i32, C.c_int64, C.c_float, vp, i32, i32, i32, vp, C.c_int64, vp]
+    lib.wm_resample_channels.argtypes = [vp, i32, i32, C.c_int64, C.c_float, vp, i32, i32, i32, vp, C.c_int64, C.c_int64, vp]
+    lib.wm_channel_top_workspace_bytes.argtypes = [i32, C.c_int64]
+    lib.wm_channel_top_workspace_bytes.restype = sz
+    lib.wm_channel_top.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, C.c_int64, vp]
     lib.wm_forced_probs.argtypes = [vp, i32, i32, i32, C.c_int64, C.c_int64, i32, vp, i32, vp, i32, vp]
     lib.wm_section_cuts_workspace_bytes.argtypes = [i32, C.c_int64]
     lib.wm_section_cuts_workspace_bytes.restype = sz

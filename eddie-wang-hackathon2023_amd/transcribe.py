@@ -40,6 +40,14 @@ longform.py states the contract (the rules and the schedule, on the host, tested
     stretches, so it cannot invent text over them, and a file with 40 % pauses has 40 % fewer windows.  An energy rule, not a
     trained voice-activity model, and its defaults are parameters, not measurements.  Without the option nothing of this runs.
 
+  * `channels` (channels.ChannelOptions): a recording's channels are kept apart instead of downmixed.
+    "split": every channel has a log-mel of its own (resampled by wm_resample_channels: all channels in one launch), the channels
+    take the rows that files take otherwise -- through `speech`, `sections` and everything above -- and channels.merge_channels
+    sorts their segments by time into `segments` and `turns`; `bleed_db` first silences a channel where another one is much
+    louder.  "label": the downmix is transcribed as ever and every segment and word gets the channel that was loudest while it was
+    spoken.  Both rest on ONE wm_channel_top call for all recordings (csrc/channels.hip).  It tells CHANNELS apart, not speakers
+    inside one, by absolute loudness; the values are parameters nobody has tuned.  Without the option nothing of this runs.
+
 Refused (ValueError): an instance built with `prompt` / `prefix` (use `initial_prompt`), conditioning or an initial prompt on
 an instance without `row_prompts`, beam_size / best_of together with a ladder of more than one temperature, and word timestamps
 with beam_size / best_of -- unless the instance shares its cross K/V (WhisperDecoding(shared_cross_kv=True): word timestamps for
@@ -53,7 +61,7 @@ several channels are downmixed and resampled to 16 kHz on the device (whisper_ut
 CLI: python transcribe.py --engine_dir eng --input_file a.flac [b.flac ...] --vocab multilingual.tiktoken [--temperature T ...]
 [--no_fallback] [--condition_on_previous_text] [--initial_prompt TEXT] [--word_timestamps] [--sections [--section_seconds S]
 [--min_section_seconds S]] [--skip_silence [--silence_margin_db D] [--min_silence_seconds S] [--min_speech_seconds S]
-[--speech_pad_seconds S]] [--beam_size K [--patience P]] [--best_of M] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
+[--speech_pad_seconds S]] [--channels split|label [--bleed_db D]] [--beam_size K [--patience P]] [--best_of M] prints one "[mm:ss.mmm --> mm:ss.mmm] text"
 line per non-empty segment, and with --word_timestamps one "start-end word (probability)" line per word under it.
 """
 from __future__ import annotations
@@ -69,11 +77,13 @@ import numpy as np
 import torch
 
 import biasing
+import channels as channels_mod
 import truncation
 import longform
 import native
 import sections as sections_mod
 import speech as speech_mod
+from channels import ChannelOptions
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 from sections import SectionOptions
@@ -269,12 +279,110 @@ def section_mels(mels: Sequence[torch.Tensor], content_frames: Sequence[int], cu
     return out, content, owner, starts
 
 
+def channel_top(mels: Sequence[torch.Tensor], content_frames: Sequence[int], channel_counts: Sequence[int], options: ChannelOptions,
+                window: int = 3000):
+    """(top, gated): per recording `top` as uint8 numpy [F] (channels.py, rule 3) and per channel the number of frames the gate
+    silenced (rule 4; zero without `bleed_db`) -- channels.channel_top_ref on the device: ONE wm_channel_top call for all
+    recordings on the current stream and one copy back.  mels: the channels of all recordings, those of a recording adjacent
+    (channel_counts[r] of them, equal in shape and content), contiguous fp16 [n_mels, >= content] on the GPU; with `bleed_db` the
+    gated columns are overwritten IN PLACE."""
+    n_rec, n_ch = len(channel_counts), len(mels)
+    if n_rec == 0:
+        return [], []
+    table, n_mels = _mel_table(mels, content_frames, "channel_top")
+    h, step = options.frames(window, n_mels)
+    first = [0]
+    for r, c in enumerate(channel_counts):
+        mine = range(first[-1], first[-1] + int(c))
+        if not 1 <= c <= channels_mod.MAX_CHANNELS or mine.stop > n_ch:
+            raise ValueError(f"channel_top: recording {r} has {c} channels (1 .. {channels_mod.MAX_CHANNELS}) of {n_ch} mels")
+        if any(mels[i].shape != mels[mine.start].shape or int(content_frames[i]) != int(content_frames[mine.start]) for i in mine):
+            raise ValueError(f"channel_top: the channels of recording {r} differ in shape or content")
+        first.append(mine.stop)
+    if first[-1] != n_ch:
+        raise ValueError(f"channel_top: channel_counts {list(channel_counts)} name {first[-1]} of {n_ch} mels")
+    dev = mels[0].device
+    frames = [int(content_frames[first[r]]) for r in range(n_rec)]
+    total = int(sum(int(c) for c in content_frames))
+    starts = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+    out = torch.empty(int(starts[-1]) + 4 * (n_rec + n_ch) + 8, dtype=torch.uint8, device=dev)       # n_top [n_rec], counts [n_ch], then top
+    ints = out[: 4 * (n_rec + n_ch)].view(torch.int32)
+    top0 = out.data_ptr() + 4 * (n_rec + n_ch)
+    ptrs = torch.tensor([top0 + int(s) for s in starts[:-1]], dtype=torch.int64).to(dev, non_blocking=False)
+    first_dev = torch.tensor(first, dtype=torch.int32).to(dev, non_blocking=False)
+    ld, content = table[1].to(torch.int32), table[2].to(torch.int32)
+    lib = native.load_library()
+    ws_bytes = int(lib.wm_channel_top_workspace_bytes(n_ch, total))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    native.check(lib.wm_channel_top(table[0].data_ptr(), ld.data_ptr(), content.data_ptr(), first_dev.data_ptr(), n_rec, n_ch, n_mels,
+                                    h, step, ptrs.data_ptr(), ints.data_ptr(), ints[n_rec:].data_ptr(), ws.data_ptr(), ws_bytes, total,
+                                    torch.cuda.current_stream(dev).cuda_stream), "wm_channel_top")
+    host = out.cpu().numpy()
+    head = host[: 4 * (n_rec + n_ch)].view(np.int32)
+    if head[:n_rec].tolist() != frames:
+        raise ValueError(f"channel_top: wm_channel_top reports {head[:n_rec].tolist()} frames for recordings of {frames}")
+    tops = host[4 * (n_rec + n_ch):]
+    return [tops[int(a): int(b)].copy() for a, b in zip(starts[:-1], starts[1:])], [int(v) for v in head[n_rec:]]
+
+
+def _transcribe_channels(encoding, decoding, mels, content_frames, channel_counts, options: ChannelOptions, speech, sections,
+                         downmix=None, **kw) -> List[dict]:
+    """`channels`: the layer outside speech / sections / files.  mels: the channels of all recordings (channel_counts[r] adjacent
+    ones per recording).  "split": one wm_channel_top call (with `bleed_db` it gates the mels, on copies), the channels
+    transcribed as files, channels.merge_channels per recording.  "label": `downmix` = (mels, content frames) of the recordings'
+    downmixes is transcribed as ever and channels.label_segments names every segment's and word's channel."""
+    options.check()
+    n_rec = len(channel_counts)
+    if len(content_frames) != len(mels):
+        raise ValueError(f"transcribe: {len(content_frames)} content_frames for {len(mels)} mels")
+    if sum(int(c) for c in channel_counts) != len(mels):
+        raise ValueError(f"transcribe: channel_counts {list(channel_counts)} for {len(mels)} channel mels")
+    ladder = kw['temperatures']
+    check_supported(decoding, tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])),
+                    kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
+    if n_rec == 0:
+        return []
+    W = 2 * decoding.decoder_config['num_audio_ctx']
+    fs = longform.CHUNK_LENGTH / W
+    gate = options.bleed_db is not None
+    mels = [m.to(torch.float16).clone() if gate and m.dtype == torch.float16 and m.is_contiguous() else m.to(torch.float16).contiguous()
+            for m in mels]                                                          # (the gate writes in place: never into the caller's)
+    content_frames = [int(c) for c in content_frames]
+    tops, gated = channel_top(mels, content_frames, channel_counts, options, window=W)
+
+    def inner(ms, cs):
+        if speech is not None:
+            return _transcribe_speech(encoding, decoding, ms, cs, speech, sections, **kw)
+        if sections is not None:
+            return _transcribe_sections(encoding, decoding, ms, cs, sections, **kw)
+        return _transcribe_files(encoding, decoding, ms, cs, None, **kw)
+
+    out, at = [], 0
+    if options.mode == "label":
+        results = inner(*downmix)
+        for r, (res, C) in enumerate(zip(results, channel_counts)):
+            res = dict(res)
+            res['segments'] = channels_mod.label_segments(res['segments'], tops[r], fs, int(C))
+            res['channel_top'] = channels_mod.run_lengths(tops[r])
+            out.append(res)
+        return out
+    parts = inner(mels, content_frames)
+    for r, C in enumerate(channel_counts):
+        res = channels_mod.merge_channels(parts[at: at + int(C)])
+        res['channel_top'] = channels_mod.run_lengths(tops[r])
+        res['channel_gated'] = gated[at: at + int(C)]
+        out.append(res)
+        at += int(C)
+    return out
+
+
 def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: Sequence[torch.Tensor],
                    content_frames: Sequence[int], *, temperatures: Sequence[float] = longform.TEMPERATURES,
                    compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
                    no_speech_threshold: Optional[float] = 0.6, n_rows: Optional[int] = None, trace: Optional[list] = None,
                    condition_on_previous_text: bool = False, initial_prompt=None, word_timestamps: bool = False,
-                   sections: Optional[SectionOptions] = None, speech: Optional[SpeechOptions] = None) -> List[dict]:
+                   sections: Optional[SectionOptions] = None, speech: Optional[SpeechOptions] = None,
+                   channels: Optional[ChannelOptions] = None, channel_counts: Optional[Sequence[int]] = None) -> List[dict]:
     """Transcribe files given as log-mels: mels[f] fp16 [n_mels, content_frames[f] + W] on the GPU (W = 2 * n_audio_ctx; the last
     W frames are the log-mel of 30 s of padding: whisper_utils.long_log_mel_device).  One dict per file: language, text, segments;
     a segment: seek, start, end (seconds), text, tokens, temperature, avg_logprob, compression_ratio, no_speech_prob.
@@ -294,10 +402,22 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
     files, those are transcribed as above (`trace`, `seek` inside it and the sections' cuts speak of the packed files), and every
     time of the result is moved back into the original file (speech.restore); a file's result also carries "speech":
     [(start, end), ...] in seconds.  A file without speech has no segments, an empty text and the language the options name
-    (None if none is named)."""
+    (None if none is named).
+    `channels` with `channel_counts` = [C_r, ...] (module docstring; channels.py): the mels are the CHANNELS of recordings,
+    channel_counts[r] adjacent ones per recording, and the result is one dict per recording -- mode "split" only (its `channels`,
+    merged `segments`, `turns`, `text`, `language`, `channel_top` as run lengths, `channel_gated`); the rows' "files" are the
+    channels.  Mode "label" needs the downmix beside the channels: `transcribe()` over files has both.  Either argument without
+    the other is refused."""
     kw = dict(temperatures=temperatures, compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
               no_speech_threshold=no_speech_threshold, n_rows=n_rows, trace=trace, condition_on_previous_text=condition_on_previous_text,
               initial_prompt=initial_prompt, word_timestamps=word_timestamps)
+    if channels is not None or channel_counts is not None:
+        if channels is None or channel_counts is None:
+            raise ValueError("transcribe_mel: `channels` goes with `channel_counts` (the mels given per channel); mels of downmixes have "
+                             "no channels to tell apart")
+        if channels.check().mode != "split":
+            raise ValueError("transcribe_mel: channels mode 'label' needs the downmix beside the channels: use transcribe() over files")
+        return _transcribe_channels(encoding, decoding, mels, content_frames, channel_counts, channels, speech, sections, **kw)
     if speech is not None:
         return _transcribe_speech(encoding, decoding, mels, content_frames, speech, sections, **kw)
     if sections is not None:
@@ -481,10 +601,51 @@ def _transcribe_files(encoding: WhisperEncoding, decoding: WhisperDecoding, mels
     return out
 
 
-def transcribe(encoding: WhisperEncoding, decoding: WhisperDecoding, audio_or_paths, **kw) -> List[dict]:
+def _transcribe_recordings(encoding, decoding, audio_or_paths, options: ChannelOptions, **kw) -> List[dict]:
+    """`transcribe` with `channels`: the channels of every file as waveforms (whisper_utils.load_audio_device(channels="split")),
+    one log-mel per channel -- each clamped to its own max - 8, as a mono file holding that channel is -- and for "label" the
+    downmix as `transcribe` has always made it."""
+    import whisper_utils as wu
+    options.check()
+    if not all(isinstance(a, (str, Path)) for a in audio_or_paths):             # refused before anything is loaded or decoded
+        raise ValueError("transcribe: `channels` needs files: a waveform handed over is a mono waveform at 16 kHz and has no channels to "
+                         "tell apart (mels per channel: transcribe_mel(..., channel_counts=...))")
+    speech, sections = kw.pop('speech', None), kw.pop('sections', None)
+    defaults = dict(temperatures=longform.TEMPERATURES, compression_ratio_threshold=2.4, logprob_threshold=-1.0, no_speech_threshold=0.6,
+                    n_rows=None, trace=None, condition_on_previous_text=False, initial_prompt=None, word_timestamps=False)
+    unknown = set(kw) - set(defaults)
+    if unknown:
+        raise TypeError(f"transcribe: unexpected arguments {sorted(unknown)}")
+    kw = {**defaults, **kw}
+    ladder = kw['temperatures']
+    check_supported(decoding, tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])),
+                    kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
+    mels, content, counts, mono_mels, mono_content = [], [], [], [], []
+    for a in audio_or_paths:
+        wave = wu.load_audio_device(str(a), channels="split")
+        mono = wu.load_audio_device(str(a)) if options.mode == "label" else None
+        for c in range(wave.shape[0]):
+            mel, frames = wu.long_log_mel_device(wave[c].contiguous())
+            mels.append(mel)
+            content.append(frames)
+        counts.append(int(wave.shape[0]))
+        if mono is not None:
+            mel, frames = wu.long_log_mel_device(mono.float().flatten())
+            mono_mels.append(mel)
+            mono_content.append(frames)
+    return _transcribe_channels(encoding, decoding, mels, content, counts, options, speech, sections,
+                                downmix=(mono_mels, mono_content) if options.mode == "label" else None, **kw)
+
+
+def transcribe(encoding: WhisperEncoding, decoding: WhisperDecoding, audio_or_paths, channels: Optional[ChannelOptions] = None,
+               **kw) -> List[dict]:
     """`transcribe_mel` over files (FLAC / WAV paths at any rate, any channel count: whisper_utils.load_audio_device resamples on
     the GPU) or waveforms (float arrays or tensors at 16 kHz): the log-mel of each whole file comes from one wm_log_mel call
-    (whisper_utils.long_log_mel_device)."""
+    (whisper_utils.long_log_mel_device).  `channels` (channels.ChannelOptions): the channels of a recording
+    are kept apart -- "split": transcribed one by one and merged by time, "label": the downmix with every segment's loudest
+    channel; a mono waveform is refused, a one-channel file is its own channel 0.  Without it nothing of that runs."""
+    if channels is not None:
+        return _transcribe_recordings(encoding, decoding, list(audio_or_paths), channels, **kw)
     import whisper_utils as wu
     mels, content = [], []
     for a in audio_or_paths:
@@ -542,9 +703,28 @@ def parse_arguments(argv=None):
                              'ONE temperature: give exactly one --temperature above 0 (a per-call temperature, i.e. the ladder, is refused)')
     parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
     parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
+    parser.add_argument('--channels', type=str, default=None, metavar='split|label',
+                        help="keep a recording's channels apart: 'split' transcribes every channel on its own and merges by time, 'label' "
+                             "transcribes the downmix and names every segment's loudest channel (whisper.cpp's --diarize); prints 'chN:' "
+                             'in front of every segment.  Channels, not speakers; absolute loudness, no level matching')
+    parser.add_argument('--bleed_db', type=float, default=None,
+                        help="with --channels split: silence a channel's frames where another channel is louder by this many dB "
+                             '(microphones that hear each other; off by default -- on a telephone line it would mute the quieter party '
+                             'of an overlap; an untuned parameter)')
     biasing.add_arguments(parser)
     truncation.add_arguments(parser)
     return parser.parse_args(argv)
+
+
+def channel_options_from_args(args) -> Optional[ChannelOptions]:
+    """The ChannelOptions of the command line (None without --channels); ValueError for an unknown mode, --bleed_db without
+    --channels split, or a --bleed_db out of range."""
+    mode, bleed = getattr(args, 'channels', None), getattr(args, 'bleed_db', None)
+    if mode is None:
+        if bleed is not None:
+            raise ValueError("--bleed_db needs --channels split")
+        return None
+    return ChannelOptions(mode=mode, bleed_db=bleed).check()
 
 
 def build_decoding(args, engine_dir, prompted: bool) -> WhisperDecoding:
@@ -571,6 +751,7 @@ def build_decoding(args, engine_dir, prompted: bool) -> WhisperDecoding:
 
 def main(args) -> List[dict]:
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.ERROR))
+    channel_options = channel_options_from_args(args)
     torch.cuda.set_device(0)
     engine_dir = Path(args.engine_dir)
     encoding = WhisperEncoding(engine_dir)
@@ -581,6 +762,7 @@ def main(args) -> List[dict]:
                          condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt,
                          word_timestamps=args.word_timestamps,
                          sections=SectionOptions(args.section_seconds, args.min_section_seconds) if args.sections else None,
+                         **(dict(channels=channel_options) if channel_options is not None else {}),
                          **(dict(speech=SpeechOptions(margin_db=args.silence_margin_db, min_silence_seconds=args.min_silence_seconds,
                                                       min_speech_seconds=args.min_speech_seconds,
                                                       speech_pad_seconds=args.speech_pad_seconds)) if args.skip_silence else {}))
@@ -588,10 +770,13 @@ def main(args) -> List[dict]:
         if len(results) > 1:
             print(f"{path} ({result['language']})")
         if args.skip_silence:
-            print("speech: " + (", ".join(f"{format_timestamp(a)} --> {format_timestamp(b)}" for a, b in result['speech']) or "none"))
+            for c, part in enumerate(result['channels']) if 'speech' not in result else [(None, result)]:
+                print(("speech: " if c is None else f"speech ch{c}: ")
+                      + (", ".join(f"{format_timestamp(a)} --> {format_timestamp(b)}" for a, b in part['speech']) or "none"))
         for s in result['segments']:
             if s['text'].strip():
-                print(f"[{format_timestamp(s['start'])} --> {format_timestamp(s['end'])}] {s['text'].strip()}")
+                who = "" if channel_options is None else ("ch?: " if s['channel'] is None else f"ch{s['channel']}: ")
+                print(f"[{format_timestamp(s['start'])} --> {format_timestamp(s['end'])}] {who}{s['text'].strip()}")
                 for w in s.get('words', ()):
                     print(f"{w['start']:.2f}\u2013{w['end']:.2f} {w['word'].strip()} ({w['probability']:.2f})")
     return results

@@ -167,11 +167,12 @@ def _device_table(rate: int, device: torch.device):
 _PCM_DTYPES = {torch.float32: 0, torch.int16: 1, torch.int32: 2}
 
 
-def resample_device(pcm: torch.Tensor, rate: int, bits: Optional[int] = None) -> torch.Tensor:
+def resample_device(pcm: torch.Tensor, rate: int, bits: Optional[int] = None, split: bool = False) -> torch.Tensor:
     """`pcm` [n, C] or [n] on the GPU (float32, or int16 / int32 PCM of `bits` bits; 1..8 interleaved channels) at `rate` Hz ->
     mono fp32 [ceil(n * 16000 / rate)] at 16 kHz on the GPU: downmix, conversion and the polyphase filter in one launch
-    (wm_resample, csrc/resample.hip), on the current stream of the tensor's device.  No CPU fallback: without the native library
-    this raises."""
+    (wm_resample, csrc/resample.hip), on the current stream of the tensor's device.  `split`: the channels are kept apart --
+    fp32 [C, ceil(n * 16000 / rate)], row c bit for bit what a mono input holding channel c gives (wm_resample_channels: all
+    channels in one launch; channels.py, rule 1).  No CPU fallback: without the native library this raises."""
     import native
     assert pcm.is_cuda and pcm.dtype in _PCM_DTYPES, "pcm must be a float32 / int16 / int32 tensor on the GPU"
     assert pcm.dim() in (1, 2)
@@ -187,8 +188,14 @@ def resample_device(pcm: torch.Tensor, rate: int, bits: Optional[int] = None) ->
         scale = 2.0 ** -(bits - 1)
     L, M, half, table = _device_table(rate, p.device)
     n_out = -(-n_in * L // M)
-    out = torch.empty(n_out, dtype=torch.float32, device=p.device)
     s = torch.cuda.current_stream(p.device).cuda_stream
+    if split:
+        out = torch.empty((channels, n_out), dtype=torch.float32, device=p.device)
+        native.check(native.load_library().wm_resample_channels(p.data_ptr(), _PCM_DTYPES[pcm.dtype], channels, n_in, scale,
+                                                                table.data_ptr(), L, M, half, out.data_ptr(), n_out, n_out, s),
+                     "wm_resample_channels")
+        return out
+    out = torch.empty(n_out, dtype=torch.float32, device=p.device)
     native.check(native.load_library().wm_resample(p.data_ptr(), _PCM_DTYPES[pcm.dtype], channels, n_in, scale, table.data_ptr(),
                                                    L, M, half, out.data_ptr(), n_out, s), "wm_resample")
     return out
@@ -279,13 +286,30 @@ def load_audio(file: str, sr: int = SAMPLE_RATE) -> np.ndarray:
     return _mono_at_sr(samples, bits)
 
 
-def load_audio_device(file: str) -> torch.Tensor:
+def channels_at_sr(samples: np.ndarray, bits: Optional[int]) -> np.ndarray:
+    """fp32 [C, n]: every channel of a file already at the wanted rate, each `_mono_at_sr` of its one column (channels.py, rule 1)."""
+    samples = samples.reshape(samples.shape[0], -1)
+    return np.stack([_mono_at_sr(samples[:, c:c + 1], bits) for c in range(samples.shape[1])])
+
+
+def load_audio_device(file: str, channels: Optional[str] = None) -> torch.Tensor:
     """`load_audio` with the result on the GPU, fp32 [n] at 16 kHz: a file at 16 kHz is the upload of load_audio's waveform; any
-    other rate is resample_device of the uploaded PCM -- the samples never come back to the host.  One decode either way."""
+    other rate is resample_device of the uploaded PCM -- the samples never come back to the host.  One decode either way.
+    `channels="split"`: fp32 [C, n], the channels kept apart (channels.py, rule 1: resample_device(split=True), or the host's
+    channels_at_sr for a file at 16 kHz); at most 8 channels."""
     file = str(file)
+    if channels not in (None, "split"):
+        raise ValueError(f"load_audio_device: channels={channels!r} is not None or 'split'")
     if file.endswith(".npy"):
-        return torch.from_numpy(load_audio(file)).cuda()
+        mono = torch.from_numpy(load_audio(file)).cuda()
+        return mono[None] if channels else mono
     samples, rate, bits = load_pcm(file)
+    if channels:
+        if not 1 <= samples.shape[1] <= 8:
+            raise ValueError(f"load_audio_device: {file} has {samples.shape[1]} channels (1 .. 8 can be kept apart)")
+        if rate == SAMPLE_RATE:
+            return torch.from_numpy(channels_at_sr(samples, bits)).cuda()
+        return resample_device(torch.from_numpy(np.ascontiguousarray(samples)).cuda(), rate, bits, split=True)
     if rate == SAMPLE_RATE:
         return torch.from_numpy(_mono_at_sr(samples, bits)).cuda()
     return resample_device(torch.from_numpy(np.ascontiguousarray(samples)).cuda(), rate, bits)

@@ -73,7 +73,8 @@ typedef struct wm_dims {
  *      (still 8: an entry and a struct of its own) wm_repeat_controls / wm_repeat_io
  *      (still 8: a test-only entry and a struct of its own) wm_attn_encoder_ex / wm_attn_encoder_io
  *      (still 8: an entry and structs of its own) wm_sequence_bias / wm_bias_io / wm_bias_item
- *      (still 8: an entry and a struct of its own) wm_sample_step / wm_sample_io */
+ *      (still 8: an entry and a struct of its own) wm_sample_step / wm_sample_io
+ *      (still 8: entries only) wm_resample_channels, wm_channel_top, wm_channel_top_workspace_bytes */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -727,6 +728,28 @@ int wm_speech_spans(const void* const* src, const int32_t* src_ld, const int32_t
  * `stream`: no allocation, no host synchronisation, capturable.  Added under ABI 8 (an entry only; no struct changes). */
 int wm_mel_gather(const void* const* src, const int32_t* src_ld, const int32_t* spans, const int32_t* n_spans, int spans_ld,
                   int batch, int n_mels, int n_pad, void* const* dst, const int32_t* dst_ld, wm_stream_t stream);
+/* The loudest channel of every frame of multi-channel recordings, and the gate that silences a channel where another one is much
+ * louder (channels.py states the contract).  The batch holds n_recordings recordings; recording r is the
+ * adjacent channels first[r] .. first[r + 1] - 1 of the n_channels channels (first: DEVICE int32 [n_recordings + 1], ascending,
+ * first[n_recordings] <= n_channels; 1 .. 8 channels each), every channel a whole-file log-mel src[c] fp16 [n_mels][src_ld[c]] with
+ * content[c] frames, the channels of a recording equal in content and src_ld.  In integers, with q, s as in wm_section_cuts over
+ * every channel:
+ *   top[r][t]  = the lowest channel c (counted from first[r]) with s_c[t] = max_c' s_c'[t],              0 <= t < F
+ *   and with step >= 1:   gated_c[t] = max_{c' != c} s_c'[t] - s_c[t] >= n_mels * (2h + 1) * step        (64-bit)
+ *   v_c = the smallest finite element of src[c][:, :F] by the monotone integer key of its fp16 bits (-0 below +0); every bin of a
+ *   gated frame of channel c is overwritten with v_c IN PLACE (columns at or beyond F are not touched; a channel without a finite
+ *   element, and a recording of one channel, are never gated);  counts[c] = the gated frames of channel c (0 with step = 0).
+ * n_top[r] = F; -1, and nothing written for it, for a recording that is not 1 .. 8 channels inside the batch, whose channels differ
+ * in content or stride, or that has frames and whose last channel ends beyond total_frames in batch order (total_frames: an upper
+ * bound on the sum of content over ALL channels).  top: DEVICE array of n_recordings device pointers to uint8 [>= F] (null: not
+ * written); src, src_ld, content as in wm_section_cuts (a null channel has no frames); counts: DEVICE int32 [n_channels].
+ * Requires 0 <= step <= 32768, h >= 0, n_mels * (2h + 1) < 131072.  The workspace (wm_channel_top_workspace_bytes, 8-byte aligned)
+ * needs no initialisation.  One launch sequence for all recordings, asynchronous on `stream`: no allocation, no host
+ * synchronisation, capturable.  Added under ABI 8 (entries only; no struct changes). */
+size_t wm_channel_top_workspace_bytes(int n_channels, int64_t total_frames);
+int wm_channel_top(void* const* src, const int32_t* src_ld, const int32_t* content, const int32_t* first, int n_recordings,
+                   int n_channels, int n_mels, int h, int step, uint8_t* const* top, int32_t* n_top, int32_t* counts,
+                   void* workspace, size_t workspace_bytes, int64_t total_frames, wm_stream_t stream);
 /* zeroes rows 0 and Tpad - 1 of every utterance of buf fp16 [B][Tpad][C]. */
 int wm_zero_pad_rows(void* buf, int B, int Tpad, int C, wm_stream_t stream);
 /* ids[b] = arg-max of row b of fp16 logits (first index wins ties).  The decode loop itself uses
@@ -910,6 +933,14 @@ int wm_log_mel(const float* audio, int batch, int n_samples, int64_t audio_ld, c
  * Added under ABI 8 (an entry only; no struct changes). */
 int wm_resample(const void* pcm, int dtype, int channels, int64_t n_in, float scale, const float* table, int L, int M, int half,
                 float* out, int64_t n_out, wm_stream_t stream);
+/* The channel form of wm_resample (channels.py, rule 1): out fp32 [channels][out_ld], row c the first n_out
+ * elements of which are channel c of the input at the new rate -- the staging selects the channel instead of summing,
+ *   x_c[k] = fp32(v[k][c]) * scale,
+ * and everything else is wm_resample's: row c equals, bit for bit, wm_resample of a mono input that holds channel c.  All channels
+ * in one launch; elements n_out .. out_ld - 1 of a row are not written.  rc 1 without a launch: what wm_resample refuses, and
+ * out_ld < n_out.  Added under ABI 8 (an entry only; no struct changes). */
+int wm_resample_channels(const void* pcm, int dtype, int channels, int64_t n_in, float scale, const float* table, int L, int M,
+                         int half, float* out, int64_t out_ld, int64_t n_out, wm_stream_t stream);
 
 /* FLAC decoder (host code, no GPU needed): replaces the ffmpeg subprocess of load_audio
  * (W/whisper_utils.py:17-54) for the LibriSpeech .flac files.  wm_flac_decode writes interleaved
