@@ -52,6 +52,17 @@ def controls_on(repetition_penalty, no_repeat_ngram_size) -> bool:
     return float(repetition_penalty) != 1.0 or int(no_repeat_ngram_size) != 0
 
 
+def add_arguments(parser) -> None:
+    """The two flags run.py, summarize.py and transcribe.py share."""
+    parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
+    parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
+
+
+def options_from_args(repetition_penalty=1.0, no_repeat_ngram_size=0) -> dict:
+    """The DecodingOptions fields of the two flags (`add_arguments`)."""
+    return dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+
+
 def penalized_tokens(history: np.ndarray, eot: int) -> np.ndarray:
     """The distinct text tokens of H, ascending: each is penalised once."""
     h = np.asarray(history, dtype=np.int64).reshape(-1)

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 import biasing
-import truncation
+import logit_controls
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 
@@ -39,18 +39,12 @@ def parse_arguments(argv=None):
                         help="beam search: the beams of an utterance read one copy of its cross-attention K/V (off by default); lets --word_timestamps run with --beam_size")
     parser.add_argument('--word_timestamps', default=False, action='store_true',
                         help='print "start-end word (probability)" lines after the text (cross-attention alignment + DTW on the device; with --beam_size it needs --shared_cross_kv)')
-    parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
-    parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
-    biasing.add_arguments(parser)
-    truncation.add_arguments(parser)
+    logit_controls.add_arguments(parser)
     return parser.parse_args(argv)
 
 
 def decoding_options(args) -> DecodingOptions:
-    return DecodingOptions(beam_size=args.beam_size, patience=args.patience, repetition_penalty=args.repetition_penalty,
-                           no_repeat_ngram_size=args.no_repeat_ngram_size,
-                           **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file),
-                           **truncation.options_from_args(args.top_k, args.top_p, args.min_p))
+    return DecodingOptions(beam_size=args.beam_size, patience=args.patience, **logit_controls.options_from_args(args))
 
 
 def load_mel(input_file: str) -> torch.Tensor:
@@ -79,15 +73,12 @@ def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', inpu
              shared_cross_kv: bool = False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              hotwords: str = None, hotword_bias: float = biasing.HOTWORD_BIAS, hotword_start_bias: float = biasing.HOTWORD_START_BIAS,
              sequence_bias_file: str = None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+    options = decoding_options(argparse.Namespace(**locals()))                  # (the keywords are parse_arguments' names)
     logging.basicConfig(level=getattr(logging, log_level.upper(), logging.ERROR))
     torch.cuda.set_device(0)
     mel = load_mel(input_file).to('cuda').type(torch.float16).unsqueeze(0)
     engine_dir = Path(engine_dir)
     whisper_encoding = WhisperEncoding(engine_dir)
-    options = DecodingOptions(beam_size=beam_size, patience=patience, repetition_penalty=repetition_penalty,
-                              no_repeat_ngram_size=no_repeat_ngram_size,
-                              **biasing.options_from_args(hotwords, hotword_bias, hotword_start_bias, sequence_bias_file),
-                              **truncation.options_from_args(top_k, top_p, min_p))
     whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=options, shared_cross_kv=shared_cross_kv)
     begin_time = time.time()
     audio_features = whisper_encoding.get_audio_features(mel)

@@ -21,8 +21,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-import biasing
-import truncation
+import logit_controls
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
 from normalizers import EnglishTextNormalizer
@@ -350,18 +349,12 @@ def parse_arguments(argv=None):
     parser.add_argument('--patience', type=float, default=None, help='beam search: finished candidates per utterance = beam_size * patience')
     parser.add_argument('--shared_cross_kv', default=False, action='store_true',
                         help="beam search: the beams of an utterance read one copy of its cross-attention K/V (off by default)")
-    parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
-    parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
-    biasing.add_arguments(parser)
-    truncation.add_arguments(parser)
+    logit_controls.add_arguments(parser)
     return parser.parse_args(argv)
 
 
 def decoding_options(args) -> DecodingOptions:
-    return DecodingOptions(beam_size=args.beam_size, patience=args.patience, repetition_penalty=args.repetition_penalty,
-                           no_repeat_ngram_size=args.no_repeat_ngram_size,
-                           **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file),
-                           **truncation.options_from_args(args.top_k, args.top_p, args.min_p))
+    return DecodingOptions(beam_size=args.beam_size, patience=args.patience, **logit_controls.options_from_args(args))
 
 
 if __name__ == '__main__':

@@ -48,6 +48,12 @@ longform.py states the contract (the rules and the schedule, on the host, tested
     spoken.  Both rest on ONE wm_channel_top call for all recordings (csrc/channels.hip).  It tells CHANNELS apart, not speakers
     inside one, by absolute loudness; the values are parameters nobody has tuned.  Without the option nothing of this runs.
 
+This module is the orchestration and the CLI.  Every entry point runs ONE preamble (`_prepare`: the lengths, the refusals below, the
+fp16 batch); `channels`, `speech` and `sections` each split the prepared batch into the batch of the layer below and a function that
+puts its results back, and `_transcribe_layers` composes them once over `_transcribe_files`.  What touches a `wm_*` mel entry point
+-- the ragged batch with its validation and its device table (uploaded once, read by every layer), and the wrappers `mel_windows`,
+`section_cuts`, `speech_spans`, `packed_mels`, `section_mels`, `channel_top` -- is mel_batch.py; the names are re-exported here.
+
 Refused (ValueError): an instance built with `prompt` / `prefix` (use `initial_prompt`), conditioning or an initial prompt on
 an instance without `row_prompts`, beam_size / best_of together with a ladder of more than one temperature, and word timestamps
 with beam_size / best_of -- unless the instance shares its cross K/V (WhisperDecoding(shared_cross_kv=True): word timestamps for
@@ -76,9 +82,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-import biasing
 import channels as channels_mod
-import truncation
+import logit_controls
 import longform
 import native
 import sections as sections_mod
@@ -86,6 +91,7 @@ import speech as speech_mod
 from channels import ChannelOptions
 from decoding import DecodingOptions, WhisperDecoding
 from encoding import WhisperEncoding
+from mel_batch import MelBatch, channel_top, mel_windows, packed_mels, section_cuts, section_mels, speech_spans  # noqa: F401 (re-exported)
 from sections import SectionOptions
 from speech import SpeechOptions
 from tokenizer import Tokenizer
@@ -113,28 +119,6 @@ def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], co
                              f"({opt.temperature}; no fallback), not the ladder {tuple(temperatures)}")
 
 
-def mel_windows(mels: Sequence[Optional[torch.Tensor]], seeks: Sequence[int], n_mels: int, n_window: int,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp16 [len(mels), n_mels, n_window]: row b is mels[b][:, seeks[b] : seeks[b] + n_window], zero behind the mel's end and
-    all zero for a None entry (wm_mel_windows: one launch for the ragged batch, on the current stream)."""
-    n = len(mels)
-    assert n >= 1 and len(seeks) == n
-    dev = next((m.device for m in mels if m is not None), out.device if out is not None else torch.device("cuda"))
-    for m in mels:
-        assert m is None or (m.is_cuda and m.dtype == torch.float16 and m.dim() == 2 and m.shape[0] == n_mels and m.is_contiguous()), \
-            "a mel must be a contiguous fp16 [n_mels, frames] tensor on the GPU"
-    table = torch.tensor([[0 if m is None else m.data_ptr() for m in mels],
-                          [0 if m is None else m.shape[1] for m in mels],
-                          [int(s) for s in seeks]], dtype=torch.int64).to(dev, non_blocking=False)
-    frames, seek = table[1].to(torch.int32), table[2].to(torch.int32)
-    if out is None:
-        out = torch.empty((n, n_mels, n_window), dtype=torch.float16, device=dev)
-    assert out.shape == (n, n_mels, n_window) and out.dtype == torch.float16 and out.is_contiguous()
-    native.check(native.load_library().wm_mel_windows(table[0].data_ptr(), frames.data_ptr(), seek.data_ptr(), n, n_mels, n_window,
-                                                      out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "wm_mel_windows")
-    return out
-
-
 def word_pass_bytes_per_row(decoding: WhisperDecoding) -> int:
     """What a row of the word-timestamp pass holds beside the decoder state: the tape of the alignment heads' queries
     (heads x L_max x 64 fp16 = 128 B each, L_max the longest forced sequence: sot_sequence + <|notimestamps|> + sample_len + EOT,
@@ -154,226 +138,130 @@ def default_rows(decoding: WhisperDecoding, n_files: int, device, word_timestamp
     return max(1, min(n_files, int(0.8 * free // per_row)))
 
 
-def section_cuts(mels: Sequence[torch.Tensor], content_frames: Sequence[int], options: SectionOptions,
-                 window: int = 3000) -> List[List[int]]:
-    """The cut frames of every file, ascending (sections.section_cuts_ref on the device: ONE wm_section_cuts launch for all files on
-    the current stream and one copy of the cuts and their counts back).  mels[f]: contiguous fp16 [n_mels, >= content_frames[f]]
-    on the GPU; `window`: the model's 2 * n_audio_ctx, which fixes the seconds per frame."""
-    n = len(mels)
-    if n == 0:
-        return []
-    if len(content_frames) != n:
-        raise ValueError(f"section_cuts: {len(content_frames)} content_frames for {n} mels")
-    n_mels = int(mels[0].shape[0])
-    lo, hi, h = options.frames(window, n_mels)
-    for m, c in zip(mels, content_frames):
-        assert m.is_cuda and m.dtype == torch.float16 and m.dim() == 2 and m.shape[0] == n_mels and m.is_contiguous(), \
-            "a mel must be a contiguous fp16 [n_mels, frames] tensor on the GPU"
-        if not 0 <= c <= m.shape[1]:
-            raise ValueError(f"section_cuts: {c} frames of content in a mel of {m.shape[1]}")
-    dev = mels[0].device
-    total = int(sum(content_frames))
-    cuts_ld = max(1, max(int(c) for c in content_frames) // lo)
-    table = torch.tensor([[m.data_ptr() for m in mels], [m.shape[1] for m in mels], [int(c) for c in content_frames]],
-                         dtype=torch.int64).to(dev, non_blocking=False)
-    ld, content = table[1].to(torch.int32), table[2].to(torch.int32)
-    lib = native.load_library()
-    ws_bytes = int(lib.wm_section_cuts_workspace_bytes(n, total))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(n * (1 + cuts_ld), dtype=torch.int32, device=dev)             # n_cuts [n], then cuts [n][cuts_ld]
-    native.check(lib.wm_section_cuts(table[0].data_ptr(), ld.data_ptr(), content.data_ptr(), n, n_mels, lo, hi, h,
-                                     out[n:].data_ptr(), cuts_ld, out.data_ptr(), ws.data_ptr(), ws_bytes, total,
-                                     torch.cuda.current_stream(dev).cuda_stream), "wm_section_cuts")
-    host = out.cpu().tolist()
-    found = host[:n]
-    if any(k < 0 or k > cuts_ld for k in found):
-        raise ValueError(f"section_cuts: wm_section_cuts found {found} cuts, room for {cuts_ld} per file")
-    return [host[n + f * cuts_ld: n + f * cuts_ld + found[f]] for f in range(n)]
+def _checked(decoding, kw: dict) -> dict:
+    """`kw` with the ladder as a tuple of floats, once check_supported has let it pass: before any tensor is touched."""
+    ladder = kw['temperatures']
+    kw = dict(kw, temperatures=tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])))
+    check_supported(decoding, kw['temperatures'], kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
+    return kw
 
 
-def _mel_table(mels: Sequence[torch.Tensor], content_frames: Sequence[int], what: str):
-    """(device int64 [3, n]: pointers, row lengths, content frames; n_mels) of a ragged batch of whole-file mels."""
-    if len(content_frames) != len(mels):
-        raise ValueError(f"{what}: {len(content_frames)} content_frames for {len(mels)} mels")
-    n_mels = int(mels[0].shape[0])
-    for m, c in zip(mels, content_frames):
-        assert m.is_cuda and m.dtype == torch.float16 and m.dim() == 2 and m.shape[0] == n_mels and m.is_contiguous(), \
-            "a mel must be a contiguous fp16 [n_mels, frames] tensor on the GPU"
-        if not 0 <= c <= m.shape[1]:
-            raise ValueError(f"{what}: {c} frames of content in a mel of {m.shape[1]}")
-    table = torch.tensor([[m.data_ptr() for m in mels], [m.shape[1] for m in mels], [int(c) for c in content_frames]],
-                         dtype=torch.int64).to(mels[0].device, non_blocking=False)
-    return table, n_mels
+def _batch(decoding, mels, content_frames, own: bool = False):
+    """(the MelBatch of the mels as contiguous fp16, W = 2 * n_audio_ctx, the seconds per frame).  `own`: no mel of the batch is
+    the caller's tensor (the gate of `channels` writes in place)."""
+    W = 2 * decoding.decoder_config['num_audio_ctx']
+    half = [m.to(torch.float16).contiguous() for m in mels]
+    if own:
+        half = [h.clone() if h is m else h for h, m in zip(half, mels)]
+    return MelBatch(half, content_frames), W, longform.CHUNK_LENGTH / W
 
 
-def speech_spans(mels: Sequence[torch.Tensor], content_frames: Sequence[int], options: SpeechOptions,
-                 window: int = 3000) -> List[List[tuple]]:
-    """The speech spans [(a, b), ...] of every file in frames, ascending (speech.speech_spans_ref on the device: ONE wm_speech_spans
-    launch for all files on the current stream and one copy of the spans and their counts back).  mels[f]: contiguous fp16
-    [n_mels, >= content_frames[f]] on the GPU; `window`: the model's 2 * n_audio_ctx, which fixes the seconds per frame."""
-    n = len(mels)
-    if n == 0:
-        return []
-    table, n_mels = _mel_table(mels, content_frames, "speech_spans")
-    h, step, permille, min_silence, min_speech, pad = options.frames(window, n_mels)
-    dev = mels[0].device
-    total = int(sum(content_frames))
-    # rule (b) leaves gaps of at least min_silence frames between spans of at least one frame, and (c), (d) only take spans away
-    spans_ld = max(1, (max(int(c) for c in content_frames) + min_silence) // (1 + min_silence))
-    ld, content = table[1].to(torch.int32), table[2].to(torch.int32)
-    lib = native.load_library()
-    ws_bytes = int(lib.wm_speech_spans_workspace_bytes(n, total))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(n * (1 + 2 * spans_ld), dtype=torch.int32, device=dev)        # n_spans [n], then spans [n][spans_ld][2]
-    native.check(lib.wm_speech_spans(table[0].data_ptr(), ld.data_ptr(), content.data_ptr(), n, n_mels, h, step, permille,
-                                     min_silence, min_speech, pad, out[n:].data_ptr(), spans_ld, out.data_ptr(), ws.data_ptr(),
-                                     ws_bytes, total, torch.cuda.current_stream(dev).cuda_stream), "wm_speech_spans")
-    host = out.cpu().tolist()
-    found = host[:n]
-    if any(k < 0 or k > spans_ld for k in found):
-        raise ValueError(f"speech_spans: wm_speech_spans found {found} spans, room for {spans_ld} per file")
-    flat = [host[n + 2 * f * spans_ld: n + 2 * (f * spans_ld + found[f])] for f in range(n)]
-    return [list(zip(x[0::2], x[1::2])) for x in flat]
-
-
-def packed_mels(mels: Sequence[torch.Tensor], content_frames: Sequence[int], spans: Sequence[Sequence[tuple]], window: int):
-    """(packed mels, their content frames P): per file the columns of its spans in order, then `window` copies of its last column
-    -- speech.packed_mel_ref's bit for bit, [n_mels, P + window] each -- from ONE wm_mel_gather launch for all files."""
-    n = len(mels)
-    if n == 0:
-        return [], []
-    if len(spans) != n:
-        raise ValueError(f"packed_mels: {len(spans)} span lists for {n} mels")
-    table, n_mels = _mel_table(mels, content_frames, "packed_mels")
-    for m, c, sp in zip(mels, content_frames, spans):
-        if m.shape[1] < 1:
-            raise ValueError("packed_mels: a mel without frames")
-        speech_mod.check_spans(sp, int(c))
-    dev = mels[0].device
-    packed = [sum(b - a for a, b in sp) for sp in spans]
-    out = [torch.empty((n_mels, P + window), dtype=torch.float16, device=dev) for P in packed]
-    spans_ld = max(1, max(len(sp) for sp in spans))
-    flat = [[v for a, b in sp for v in (a, b)] + [0] * (2 * (spans_ld - len(sp))) for sp in spans]
-    ints = torch.tensor([len(sp) for sp in spans] + [P + window for P in packed] + [v for row in flat for v in row],
-                        dtype=torch.int32).to(dev, non_blocking=False)              # n_spans [n], dst_ld [n], spans [n][spans_ld][2]
-    dst = torch.tensor([o.data_ptr() for o in out], dtype=torch.int64).to(dev, non_blocking=False)
-    ld = table[1].to(torch.int32)
-    native.check(native.load_library().wm_mel_gather(table[0].data_ptr(), ld.data_ptr(), ints[2 * n:].data_ptr(), ints.data_ptr(),
-                                                     spans_ld, n, n_mels, window, dst.data_ptr(), ints[n:].data_ptr(),
-                                                     torch.cuda.current_stream(dev).cuda_stream), "wm_mel_gather")
-    return out, packed
-
-
-def section_mels(mels: Sequence[torch.Tensor], content_frames: Sequence[int], cuts: Sequence[Sequence[int]], window: int):
-    """The sections of every file as files of their own: (section mels, their content frames, owner, starts) in file order and
-    section order; owner[i] is the file of section i and starts[i] its first frame there.  A section's mel is
-    sections.section_mel_ref's bit for bit: its frames, then `window` copies of the file's last column."""
-    out, content, owner, starts = [], [], [], []
-    for f, (m, c) in enumerate(zip(mels, content_frames)):
-        pad = m[:, -1:].expand(-1, window) if c > 0 else None
-        for a, b in sections_mod.section_bounds(int(c), cuts[f]):
-            out.append(torch.cat([m[:, a:b], pad], dim=1).contiguous())
-            content.append(b - a)
-            owner.append(f)
-            starts.append(a)
-    return out, content, owner, starts
-
-
-def channel_top(mels: Sequence[torch.Tensor], content_frames: Sequence[int], channel_counts: Sequence[int], options: ChannelOptions,
-                window: int = 3000):
-    """(top, gated): per recording `top` as uint8 numpy [F] (channels.py, rule 3) and per channel the number of frames the gate
-    silenced (rule 4; zero without `bleed_db`) -- channels.channel_top_ref on the device: ONE wm_channel_top call for all
-    recordings on the current stream and one copy back.  mels: the channels of all recordings, those of a recording adjacent
-    (channel_counts[r] of them, equal in shape and content), contiguous fp16 [n_mels, >= content] on the GPU; with `bleed_db` the
-    gated columns are overwritten IN PLACE."""
-    n_rec, n_ch = len(channel_counts), len(mels)
-    if n_rec == 0:
-        return [], []
-    table, n_mels = _mel_table(mels, content_frames, "channel_top")
-    h, step = options.frames(window, n_mels)
-    first = [0]
-    for r, c in enumerate(channel_counts):
-        mine = range(first[-1], first[-1] + int(c))
-        if not 1 <= c <= channels_mod.MAX_CHANNELS or mine.stop > n_ch:
-            raise ValueError(f"channel_top: recording {r} has {c} channels (1 .. {channels_mod.MAX_CHANNELS}) of {n_ch} mels")
-        if any(mels[i].shape != mels[mine.start].shape or int(content_frames[i]) != int(content_frames[mine.start]) for i in mine):
-            raise ValueError(f"channel_top: the channels of recording {r} differ in shape or content")
-        first.append(mine.stop)
-    if first[-1] != n_ch:
-        raise ValueError(f"channel_top: channel_counts {list(channel_counts)} name {first[-1]} of {n_ch} mels")
-    dev = mels[0].device
-    frames = [int(content_frames[first[r]]) for r in range(n_rec)]
-    total = int(sum(int(c) for c in content_frames))
-    starts = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
-    out = torch.empty(int(starts[-1]) + 4 * (n_rec + n_ch) + 8, dtype=torch.uint8, device=dev)       # n_top [n_rec], counts [n_ch], then top
-    ints = out[: 4 * (n_rec + n_ch)].view(torch.int32)
-    top0 = out.data_ptr() + 4 * (n_rec + n_ch)
-    ptrs = torch.tensor([top0 + int(s) for s in starts[:-1]], dtype=torch.int64).to(dev, non_blocking=False)
-    first_dev = torch.tensor(first, dtype=torch.int32).to(dev, non_blocking=False)
-    ld, content = table[1].to(torch.int32), table[2].to(torch.int32)
-    lib = native.load_library()
-    ws_bytes = int(lib.wm_channel_top_workspace_bytes(n_ch, total))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    native.check(lib.wm_channel_top(table[0].data_ptr(), ld.data_ptr(), content.data_ptr(), first_dev.data_ptr(), n_rec, n_ch, n_mels,
-                                    h, step, ptrs.data_ptr(), ints.data_ptr(), ints[n_rec:].data_ptr(), ws.data_ptr(), ws_bytes, total,
-                                    torch.cuda.current_stream(dev).cuda_stream), "wm_channel_top")
-    host = out.cpu().numpy()
-    head = host[: 4 * (n_rec + n_ch)].view(np.int32)
-    if head[:n_rec].tolist() != frames:
-        raise ValueError(f"channel_top: wm_channel_top reports {head[:n_rec].tolist()} frames for recordings of {frames}")
-    tops = host[4 * (n_rec + n_ch):]
-    return [tops[int(a): int(b)].copy() for a, b in zip(starts[:-1], starts[1:])], [int(v) for v in head[n_rec:]]
-
-
-def _transcribe_channels(encoding, decoding, mels, content_frames, channel_counts, options: ChannelOptions, speech, sections,
-                         downmix=None, **kw) -> List[dict]:
-    """`channels`: the layer outside speech / sections / files.  mels: the channels of all recordings (channel_counts[r] adjacent
-    ones per recording).  "split": one wm_channel_top call (with `bleed_db` it gates the mels, on copies), the channels
-    transcribed as files, channels.merge_channels per recording.  "label": `downmix` = (mels, content frames) of the recordings'
-    downmixes is transcribed as ever and channels.label_segments names every segment's and word's channel."""
-    options.check()
-    n_rec = len(channel_counts)
+def _prepare(decoding, mels, content_frames, kw: dict, own: bool = False):
+    """The preamble of every entry point, run once: the lengths, the refusals, then (batch, W, seconds per frame, kw)."""
     if len(content_frames) != len(mels):
         raise ValueError(f"transcribe: {len(content_frames)} content_frames for {len(mels)} mels")
-    if sum(int(c) for c in channel_counts) != len(mels):
-        raise ValueError(f"transcribe: channel_counts {list(channel_counts)} for {len(mels)} channel mels")
-    ladder = kw['temperatures']
-    check_supported(decoding, tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])),
-                    kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
-    if n_rec == 0:
-        return []
-    W = 2 * decoding.decoder_config['num_audio_ctx']
-    fs = longform.CHUNK_LENGTH / W
-    gate = options.bleed_db is not None
-    mels = [m.to(torch.float16).clone() if gate and m.dtype == torch.float16 and m.is_contiguous() else m.to(torch.float16).contiguous()
-            for m in mels]                                                          # (the gate writes in place: never into the caller's)
-    content_frames = [int(c) for c in content_frames]
-    tops, gated = channel_top(mels, content_frames, channel_counts, options, window=W)
+    kw = _checked(decoding, kw)
+    return (*_batch(decoding, mels, content_frames, own), kw)
 
-    def inner(ms, cs):
-        if speech is not None:
-            return _transcribe_speech(encoding, decoding, ms, cs, speech, sections, **kw)
-        if sections is not None:
-            return _transcribe_sections(encoding, decoding, ms, cs, sections, **kw)
-        return _transcribe_files(encoding, decoding, ms, cs, None, **kw)
 
-    out, at = [], 0
-    if options.mode == "label":
-        results = inner(*downmix)
+# A layer splits a prepared batch into the batch the layer below transcribes and the function that puts those results back.
+def _split_channels(batch: MelBatch, W: int, fs: float, options: ChannelOptions, channel_counts, downmix: Optional[MelBatch]):
+    """`channels`.  batch: the channels of all recordings (channel_counts[r] adjacent ones per recording).  "split": one
+    wm_channel_top call (with `bleed_db` it gates the mels, which are copies), the channels transcribed as files,
+    channels.merge_channels per recording.  "label": the recordings' downmixes are transcribed as ever and
+    channels.label_segments names every segment's and word's channel."""
+    tops, gated = channel_top(batch, batch.content_frames, channel_counts, options, window=W)
+
+    def label(results):
+        out = []
         for r, (res, C) in enumerate(zip(results, channel_counts)):
             res = dict(res)
             res['segments'] = channels_mod.label_segments(res['segments'], tops[r], fs, int(C))
             res['channel_top'] = channels_mod.run_lengths(tops[r])
             out.append(res)
         return out
-    parts = inner(mels, content_frames)
-    for r, C in enumerate(channel_counts):
-        res = channels_mod.merge_channels(parts[at: at + int(C)])
-        res['channel_top'] = channels_mod.run_lengths(tops[r])
-        res['channel_gated'] = gated[at: at + int(C)]
-        out.append(res)
-        at += int(C)
-    return out
+
+    def merge(parts):
+        out, at = [], 0
+        for r, C in enumerate(channel_counts):
+            res = channels_mod.merge_channels(parts[at: at + int(C)])
+            res['channel_top'] = channels_mod.run_lengths(tops[r])
+            res['channel_gated'] = gated[at: at + int(C)]
+            out.append(res)
+            at += int(C)
+        return out
+
+    return (downmix, label) if options.mode == "label" else (batch, merge)
+
+
+def _split_speech(batch: MelBatch, W: int, fs: float, options: SpeechOptions):
+    """`speech`: find the spans, pack them; the times of the packed files' results are moved back."""
+    spans = speech_spans(batch, batch.content_frames, options, window=W)
+
+    def restore(results):
+        for r, sp in zip(results, spans):
+            r['segments'] = speech_mod.restore(r['segments'], sp, fs)
+            r['speech'] = [(a * fs, b * fs) for a, b in sp]
+            if 'sections' in r:
+                r['sections'] = [(speech_mod.restore_time(a, sp, fs), speech_mod.restore_time(b, sp, fs, end=True)) for a, b in r['sections']]
+        return results
+
+    return MelBatch(*packed_mels(batch, batch.content_frames, spans, W)), restore
+
+
+def _split_sections(batch: MelBatch, W: int, fs: float, options: SectionOptions, decoding):
+    """`sections`: cut; the sections are files that share their owner's language (`owner`, the third value), merged per file."""
+    cuts = section_cuts(batch, batch.content_frames, options, window=W)
+    pieces, piece_frames, owner, starts = section_mels(batch, batch.content_frames, cuts, W)
+
+    def merge(parts):
+        out = []
+        for f in range(len(batch)):
+            mine = [i for i, o in enumerate(owner) if o == f]
+            segments = sections_mod.merge_sections([parts[i]['segments'] for i in mine], [starts[i] for i in mine], fs)
+            text = decoding.tokenizer.decode([t for s in segments for t in s['tokens']]).strip()
+            language = parts[mine[0]]['language'] if mine else _language_without_audio(decoding)
+            out.append(dict(language=language, text=text, segments=segments,
+                            sections=[(starts[i] * fs, (starts[i] + piece_frames[i]) * fs) for i in mine]))
+        return out
+
+    return MelBatch(pieces, piece_frames), merge, owner
+
+
+def _transcribe_layers(encoding, decoding, batch: MelBatch, W: int, fs: float, kw: dict, channels=None, speech=None,
+                       sections=None) -> List[dict]:
+    """channels o speech o sections o files over a prepared batch: every layer that is asked for splits the batch of the one above
+    (`sections` inside `speech` cuts the packed mels), `_transcribe_files` decodes what is left, and the layers put the results
+    back, innermost first.  `channels`: (ChannelOptions, channel_counts, the downmixes' batch or None)."""
+    if len(batch) == 0:
+        return []
+    joins, owner = [], None
+    if channels is not None:
+        batch, join = _split_channels(batch, W, fs, *channels)
+        joins.append(join)
+    if speech is not None:
+        batch, join = _split_speech(batch, W, fs, speech)
+        joins.append(join)
+    if sections is not None:
+        batch, join, owner = _split_sections(batch, W, fs, sections, decoding)
+        joins.append(join)
+    results = _transcribe_files(encoding, decoding, batch, batch.content_frames, owner, **kw)
+    for join in reversed(joins):
+        results = join(results)
+    return results
+
+
+def _transcribe_channels(encoding, decoding, mels, content_frames, channel_counts, options: ChannelOptions, speech, sections,
+                         downmix=None, **kw) -> List[dict]:
+    """transcribe_mel with `channels` over the channels' mels; "label" also takes `downmix` = (mels, content frames) of the
+    recordings' downmixes."""
+    options.check()
+    if sum(int(c) for c in channel_counts) != len(mels):
+        raise ValueError(f"transcribe: channel_counts {list(channel_counts)} for {len(mels)} channel mels")
+    batch, W, fs, kw = _prepare(decoding, mels, content_frames, kw, own=options.bleed_db is not None)
+    if options.mode == "label":
+        downmix = _batch(decoding, *downmix)[0]
+    return _transcribe_layers(encoding, decoding, batch, W, fs, kw, (options, channel_counts, downmix), speech, sections)
 
 
 def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: Sequence[torch.Tensor],
@@ -418,68 +306,8 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
         if channels.check().mode != "split":
             raise ValueError("transcribe_mel: channels mode 'label' needs the downmix beside the channels: use transcribe() over files")
         return _transcribe_channels(encoding, decoding, mels, content_frames, channel_counts, channels, speech, sections, **kw)
-    if speech is not None:
-        return _transcribe_speech(encoding, decoding, mels, content_frames, speech, sections, **kw)
-    if sections is not None:
-        return _transcribe_sections(encoding, decoding, mels, content_frames, sections, **kw)
-    return _transcribe_files(encoding, decoding, mels, content_frames, None, **kw)
-
-
-def _transcribe_speech(encoding, decoding, mels, content_frames, options: SpeechOptions, sections, **kw) -> List[dict]:
-    """transcribe_mel with `speech`: find the spans, pack them, transcribe the packed files, move the times back."""
-    n_files = len(mels)
-    if len(content_frames) != n_files:
-        raise ValueError(f"transcribe: {len(content_frames)} content_frames for {n_files} mels")
-    ladder = kw['temperatures']
-    check_supported(decoding, tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])),
-                    kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
-    if n_files == 0:
-        return []
-    W = 2 * decoding.decoder_config['num_audio_ctx']
-    fs = longform.CHUNK_LENGTH / W
-    mels = [m.to(torch.float16).contiguous() for m in mels]
-    content_frames = [int(c) for c in content_frames]
-    spans = speech_spans(mels, content_frames, options, window=W)
-    packed, packed_frames = packed_mels(mels, content_frames, spans, W)
-    if sections is not None:
-        results = _transcribe_sections(encoding, decoding, packed, packed_frames, sections, **kw)
-    else:
-        results = _transcribe_files(encoding, decoding, packed, packed_frames, None, **kw)
-    for r, sp in zip(results, spans):
-        r['segments'] = speech_mod.restore(r['segments'], sp, fs)
-        r['speech'] = [(a * fs, b * fs) for a, b in sp]
-        if 'sections' in r:
-            r['sections'] = [(speech_mod.restore_time(a, sp, fs), speech_mod.restore_time(b, sp, fs, end=True)) for a, b in r['sections']]
-    return results
-
-
-def _transcribe_sections(encoding, decoding, mels, content_frames, options: SectionOptions, **kw) -> List[dict]:
-    """transcribe_mel with `sections`: cut, decode the sections as files that share their owner's language, merge."""
-    n_files = len(mels)
-    if len(content_frames) != n_files:
-        raise ValueError(f"transcribe: {len(content_frames)} content_frames for {n_files} mels")
-    ladder = kw['temperatures']
-    check_supported(decoding, tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])),
-                    kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
-    if n_files == 0:
-        return []
-    W = 2 * decoding.decoder_config['num_audio_ctx']
-    fs = longform.CHUNK_LENGTH / W
-    mels = [m.to(torch.float16).contiguous() for m in mels]
-    content_frames = [int(c) for c in content_frames]
-    cuts = section_cuts(mels, content_frames, options, window=W)
-    pieces, piece_frames, owner, starts = section_mels(mels, content_frames, cuts, W)
-    parts = _transcribe_files(encoding, decoding, pieces, piece_frames, owner, **kw)
-    tk = decoding.tokenizer
-    out = []
-    for f in range(n_files):
-        mine = [i for i, o in enumerate(owner) if o == f]
-        segments = sections_mod.merge_sections([parts[i]['segments'] for i in mine], [starts[i] for i in mine], fs)
-        text = tk.decode([t for s in segments for t in s['tokens']]).strip()
-        language = parts[mine[0]]['language'] if mine else _language_without_audio(decoding)
-        out.append(dict(language=language, text=text, segments=segments,
-                        sections=[(starts[i] * fs, (starts[i] + piece_frames[i]) * fs) for i in mine]))
-    return out
+    batch, W, fs, kw = _prepare(decoding, mels, content_frames, kw)
+    return _transcribe_layers(encoding, decoding, batch, W, fs, kw, None, speech, sections)
 
 
 def _named_language(decoding: WhisperDecoding) -> Optional[str]:
@@ -498,27 +326,27 @@ def _transcribe_files(encoding: WhisperEncoding, decoding: WhisperDecoding, mels
                       logprob_threshold, no_speech_threshold, n_rows, trace, condition_on_previous_text, initial_prompt,
                       word_timestamps) -> List[dict]:
     """transcribe_mel's body.  `owner`: None, or per "file" the file it is a section of: the sections of a file stand together
-    in section order and share ONE language, detected (unless named) on the first window of the first of them."""
-    temperatures = tuple(float(t) for t in (temperatures if isinstance(temperatures, (tuple, list)) else [temperatures]))
-    check_supported(decoding, temperatures, condition_on_previous_text, initial_prompt, word_timestamps)
+    in section order and share ONE language, detected (unless named) on the first window of the first of them.  The layers hand
+    it the batch they prepared; called on its own with lists it runs the preamble itself."""
+    if not isinstance(mels, MelBatch):
+        mels, _, _, kw = _prepare(decoding, mels, content_frames, dict(
+            temperatures=temperatures, condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt,
+            word_timestamps=word_timestamps))
+        temperatures = kw['temperatures']
+    content_frames = mels.content_frames
     if isinstance(initial_prompt, str):
         initial_prompt = decoding.tokenizer.encode(" " + initial_prompt.strip())
     initial_prompt = [int(t) for t in (initial_prompt if initial_prompt is not None else ())]
     prompted = bool(condition_on_previous_text) or len(initial_prompt) > 0
     n_files = len(mels)
-    if len(content_frames) != n_files:
-        raise ValueError(f"transcribe: {len(content_frames)} content_frames for {n_files} mels")
-    cfg = decoding.decoder_config
-    W = 2 * cfg['num_audio_ctx']
+    W = 2 * decoding.decoder_config['num_audio_ctx']
     tk = decoding.tokenizer
     if n_files == 0:
         return []
-    n_mels = int(mels[0].shape[0])
+    n_mels, dev = mels.n_mels, mels.device
     for f, (m, c) in enumerate(zip(mels, content_frames)):
         if m.dim() != 2 or m.shape[0] != n_mels or m.shape[1] < c or c < 0:
             raise ValueError(f"transcribe: mel {f} has shape {tuple(m.shape)} for {c} frames of content")
-    dev = mels[0].device
-    mels = [m.to(torch.float16).contiguous() for m in mels]
     if n_rows is None:
         n_rows = default_rows(decoding, max(1, sum(1 for c in content_frames if c > 0)), dev, word_timestamps)
     n_group = decoding.n_group
@@ -616,10 +444,7 @@ def _transcribe_recordings(encoding, decoding, audio_or_paths, options: ChannelO
     unknown = set(kw) - set(defaults)
     if unknown:
         raise TypeError(f"transcribe: unexpected arguments {sorted(unknown)}")
-    kw = {**defaults, **kw}
-    ladder = kw['temperatures']
-    check_supported(decoding, tuple(float(t) for t in (ladder if isinstance(ladder, (tuple, list)) else [ladder])),
-                    kw['condition_on_previous_text'], kw['initial_prompt'], kw['word_timestamps'])
+    kw = _checked(decoding, {**defaults, **kw})                                 # the preamble's refusals, before anything is loaded
     mels, content, counts, mono_mels, mono_content = [], [], [], [], []
     for a in audio_or_paths:
         wave = wu.load_audio_device(str(a), channels="split")
@@ -633,8 +458,9 @@ def _transcribe_recordings(encoding, decoding, audio_or_paths, options: ChannelO
             mel, frames = wu.long_log_mel_device(mono.float().flatten())
             mono_mels.append(mel)
             mono_content.append(frames)
-    return _transcribe_channels(encoding, decoding, mels, content, counts, options, speech, sections,
-                                downmix=(mono_mels, mono_content) if options.mode == "label" else None, **kw)
+    batch, W, fs = _batch(decoding, mels, content, own=options.bleed_db is not None)      # (and its batch, once they are)
+    downmix = _batch(decoding, mono_mels, mono_content)[0] if options.mode == "label" else None
+    return _transcribe_layers(encoding, decoding, batch, W, fs, kw, (options, counts, downmix), speech, sections)
 
 
 def transcribe(encoding: WhisperEncoding, decoding: WhisperDecoding, audio_or_paths, channels: Optional[ChannelOptions] = None,
@@ -701,8 +527,6 @@ def parse_arguments(argv=None):
     parser.add_argument('--best_of', type=int, default=None,
                         help='samples per window above temperature 0.  Without --beam_size every window is decoded as best_of samples at '
                              'ONE temperature: give exactly one --temperature above 0 (a per-call temperature, i.e. the ladder, is refused)')
-    parser.add_argument('--repetition_penalty', type=float, default=1.0, help='repetition penalty inside the decode loop: logits of text tokens already sampled are divided (positive) / multiplied (else) by it (1.0 = off; the prompt is not counted)')
-    parser.add_argument('--no_repeat_ngram_size', type=int, default=0, help='no n-gram of sampled tokens of this size may end in the same text token twice (0 = off; the prompt is not counted)')
     parser.add_argument('--channels', type=str, default=None, metavar='split|label',
                         help="keep a recording's channels apart: 'split' transcribes every channel on its own and merges by time, 'label' "
                              "transcribes the downmix and names every segment's loudest channel (whisper.cpp's --diarize); prints 'chN:' "
@@ -711,8 +535,7 @@ def parse_arguments(argv=None):
                         help="with --channels split: silence a channel's frames where another channel is louder by this many dB "
                              '(microphones that hear each other; off by default -- on a telephone line it would mute the quieter party '
                              'of an overlap; an untuned parameter)')
-    biasing.add_arguments(parser)
-    truncation.add_arguments(parser)
+    logit_controls.add_arguments(parser)
     return parser.parse_args(argv)
 
 
@@ -732,9 +555,7 @@ def build_decoding(args, engine_dir, prompted: bool) -> WhisperDecoding:
     shared copy of the cross K/V; --best_of alone: best_of samples at the one temperature given.  --repetition_penalty /
     --no_repeat_ngram_size, --hotwords / --sequence_bias_file and --top_k / --top_p / --min_p go into the instance's options: every window, temperature and section
     decodes through it."""
-    repeat = dict(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
-                  **biasing.options_from_args(args.hotwords, args.hotword_bias, args.hotword_start_bias, args.sequence_bias_file),
-                  **truncation.options_from_args(args.top_k, args.top_p, args.min_p))
+    repeat = logit_controls.options_from_args(args)
     if args.beam_size is not None:
         options = DecodingOptions(language=args.language, beam_size=args.beam_size, patience=args.patience, **repeat)
         return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,

@@ -13,7 +13,7 @@
 Tolerances: none anywhere; every comparison is of integers, of fp16 bit patterns, or of results of the same arithmetic.
 
 Measured on MI355X (printed by the tests): files of 1000, 300 and 400 frames with planted quiet stretches give the spans
-[(0, 209), (491, 709), (751, 1000)], [(0, 109), (131, 300)] and none; 9 windows with `speech`, 15 without.  The 38 tests take 5 s.
+[(0, 209), (491, 709), (751, 1000)], [(0, 109), (131, 300)] and none; 9 windows with `speech`, 15 without.  The 39 tests take 5 s.
 """
 import copy
 import os
@@ -534,6 +534,42 @@ def test_refusals_stay_and_the_plain_path_is_what_it_was(lib, engines, monkeypat
     for e, r in zip(a, b):
         assert e["rows"] == r["rows"] and e["live"] == r["live"] and torch.equal(e["windows"], r["windows"])
         assert [None if x is None else x.tokens for x in e["results"]] == [None if x is None else x.tokens for x in r["results"]]
+
+
+def test_a_mel_batch_is_validated_and_uploaded_once(lib):
+    """One mel_batch.MelBatch handed to the four wrappers that read a batch's table: each returns exactly what it returns for the
+    lists, and the table the first call uploaded is the one the last call read.  Three ragged mels at the micro engine's
+    n_mels: an odd row length, no content at all, a few hundred frames."""
+    import channels as CH
+    from mel_batch import MelBatch
+    rng = KR.philox(41)
+    n_mels, W, content = 16, 128, [77, 0, 300]
+    host = [speechlike(rng, n_mels, F + W, F) for F in content]                  # row lengths 205, 128, 428
+    mels = [torch.from_numpy(m).cuda() for m in host]
+    sec, chan = S.SectionOptions(max_seconds=30.0), CH.ChannelOptions()
+    want_cuts = T.section_cuts(mels, content, sec, window=W)
+    want_spans = T.speech_spans(mels, content, OPTS, window=W)
+    want_packed, want_frames = T.packed_mels(mels, content, want_spans, W)
+    want_tops, want_gated = T.channel_top(mels, content, [1, 1, 1], chan, window=W)
+    batch = MelBatch(mels, content)
+    assert batch.table is None and len(batch) == 3 and batch.n_mels == n_mels and batch.content_frames == content
+    assert T.section_cuts(batch, None, sec, window=W) == want_cuts and len(want_cuts[2]) >= 2
+    table = batch.table
+    assert table.is_cuda and table.dtype == torch.int64 and table.cpu().tolist() == [[m.data_ptr() for m in mels], [m.shape[1] for m in mels], content]
+    spans = T.speech_spans(batch, None, OPTS, window=W)
+    assert spans == want_spans == [SP.speech_spans_ref(m, F, *OPTS.frames(W, n_mels)) for m, F in zip(host, content)] and spans[1] == []
+    packed, frames = T.packed_mels(batch, None, spans, W)
+    assert frames == want_frames and all(torch.equal(a, b) for a, b in zip(packed, want_packed))
+    tops, gated = T.channel_top(batch, None, [1, 1, 1], chan, window=W)
+    assert gated == want_gated and all(np.array_equal(a, b) for a, b in zip(tops, want_tops))
+    assert batch.table is table
+    assert all(torch.equal(m, torch.from_numpy(h).cuda()) for m, h in zip(mels, host))
+    with pytest.raises(ValueError, match="2 content_frames for 3 mels"):
+        MelBatch(mels, content[:2], "speech_spans")
+    with pytest.raises(ValueError, match="speech_spans: 999 frames of content in a mel of 128"):
+        T.speech_spans(mels, [77, 999, 300], OPTS, window=W)
+    with pytest.raises(AssertionError, match="a mel must be a contiguous fp16"):
+        T.section_cuts([m.float() for m in mels], content, sec, window=W)
 
 
 def test_cli_skip_silence_on_flac(lib, engines, golden_dir, capsys):

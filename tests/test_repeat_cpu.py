@@ -245,3 +245,31 @@ def test_literal_loop_on_the_cpu_penalty_and_bigrams(cpu_model):
         assert not has_repeated_ngram(row[dec.sample_begin:].tolist(), 2, eot)
     ts = dec.tokenizer.timestamp_begin + 5
     assert has_repeated_ngram([7, 11, ts, 7, 11], 2, eot) and not has_repeated_ngram([7, ts, 11, 7, ts], 2, eot)      # (the checker itself)
+
+
+def test_one_command_line_gives_the_three_clis_the_same_options(tmp_path, monkeypatch):
+    """Every logit control set at once: run.py, summarize.py and transcribe.py read the flags through logit_controls and build
+    the same DecodingOptions (transcribe.py's reaches its WhisperDecoding, which is recorded here: no engine)."""
+    import logit_controls
+    import run
+    import summarize
+    import transcribe
+    seq = tmp_path / "bias.json"
+    seq.write_text("[[[5, 6], -2.0]]")
+    flags = ["--repetition_penalty", "1.3", "--no_repeat_ngram_size", "3", "--hotwords", "Kubernetes, MI355X", "--hotword_bias", "4.5",
+             "--hotword_start_bias", "1.5", "--sequence_bias_file", str(seq), "--top_k", "50", "--top_p", "0.9", "--min_p", "0.05"]
+    want = DecodingOptions(repetition_penalty=1.3, no_repeat_ngram_size=3, hotwords=("Kubernetes", "MI355X"), hotword_bias=4.5,
+                           hotword_start_bias=1.5, sequence_bias=(((5, 6), -2.0),), top_k=50, top_p=0.9, min_p=0.05)
+    assert run.decoding_options(run.parse_arguments(flags)) == want
+    assert summarize.decoding_options(summarize.parse_arguments(flags)) == want
+    built = []
+    monkeypatch.setattr(transcribe, "WhisperDecoding", lambda *a, **k: built.append(k["options"]))
+    transcribe.build_decoding(transcribe.parse_arguments(["--input_file", "a.wav"] + flags), "unused", False)
+    assert built == [want]
+    for mod, base in ((run, []), (summarize, []), (transcribe, ["--input_file", "a.wav"])):
+        args = mod.parse_arguments(base)
+        assert (args.repetition_penalty, args.no_repeat_ngram_size) == (1.0, 0)
+        assert DecodingOptions(**logit_controls.options_from_args(args)) == DecodingOptions()
+    # run.generate takes the flags as keywords and builds its options from them by parse_arguments' names: every flag is a keyword
+    import inspect
+    assert set(vars(run.parse_arguments([]))) == set(inspect.signature(run.generate).parameters)
