@@ -16,8 +16,10 @@ The plugin flags (--use_gpt_attention_plugin / --use_gemm_plugin / --use_layerno
 accepted and persisted for CLI parity.  In the reference they do not change the Whisper graph
 (they are set after tracing); here the HIP kernels are always the executed path.
 
-Extra, not in the reference: `--synthetic {large-v2,tiny.en,micro,...}` builds from a seeded
-random-init checkpoint (no checkpoint file exists on the boxes of this build), `--gelu tanh`
+Extra, not in the reference: `--synthetic {large-v2,large-v3,large-v3-turbo,distil-large-v3,tiny.en,micro,...}`
+(synthetic.DIMS) builds from a seeded random-init checkpoint (no checkpoint file exists on the boxes of this build); a
+checkpoint of the large-v3 generation -- `dims` with n_mels 128 and n_vocab 51866, from `--synthetic` or `--model_dir` --
+needs no flag of its own: the configs carry `num_mels` and `vocab_size`, which the front ends and the tokenizer follow.  `--gelu tanh`
 selects the TRT path's tanh GELU instead of the torch path's erf GELU.
 """
 from __future__ import annotations

@@ -59,7 +59,7 @@ from host_decoding import (BEAM_MAX, BEAM_POOL_MAX, CHUNK_LENGTH, ApplyTimestamp
                            GreedyDecoder, HostLoops, LogitFilter, MaximumLikelihoodRanker, NoRepeatNGram, RepetitionPenalty,
                            SequenceBias, SuppressBlank, SuppressTokens)
 from session import Session
-from tokenizer import Tokenizer
+from tokenizer import Tokenizer, layout_from_vocab
 
 
 @dataclass(frozen=True)
@@ -220,11 +220,15 @@ class WhisperDecoding(HostLoops, DeviceLoop):
         if not only_torch:
             self.decoder_session, self.cross_attn_session = self.get_session(engine_dir)
         self.vocab_path = vocab_path
-        multilingual = self.decoder_config.get('vocab_size', 51865) >= 51865
+        # the ids of every special come from the vocabulary size: 99 languages up to large-v2 (51864 / 51865 tokens), 100 from
+        # large-v3 on (51866: <|yue|>, every special behind the language block one id higher); any other real size is refused
+        multilingual, self.num_languages = layout_from_vocab(self.decoder_config.get('vocab_size', 51865))
         self.tokenizer = self.get_tokenizer(multilingual, 'en', 'transcribe')
         self.is_multilingual = multilingual
 
         self.options = options or DecodingOptions()
+        if multilingual and self.options.language is not None:       # a language this vocabulary has no token for (yue at 99) is refused here
+            Tokenizer._defaults(True, self.options.language, None, self.num_languages)
         check_decoding_options(self.options)
         check_candidate_options(self.options, bool(shared_cross_kv), fallback_best_of)
         self.shared_cross_kv = bool(shared_cross_kv)
@@ -393,8 +397,8 @@ class WhisperDecoding(HostLoops, DeviceLoop):
             bundled = Path(__file__).resolve().parent / 'assets' / ('multilingual.tiktoken' if multilingual else 'gpt2.tiktoken')
             path = str(bundled) if bundled.exists() else None
         if path:
-            return Tokenizer.from_vocab(path, multilingual, language, task)
-        return Tokenizer.ids_only(multilingual, language, task)
+            return Tokenizer.from_vocab(path, multilingual, language, task, num_languages=self.num_languages)
+        return Tokenizer.ids_only(multilingual, language, task, num_languages=self.num_languages)
 
     def _get_initial_tokens(self) -> Tuple[int]:
         tokens = list(self.sot_sequence)

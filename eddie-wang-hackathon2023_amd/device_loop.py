@@ -288,6 +288,20 @@ class DeviceLoop:
         return st['lang_logits'][::every, 0].float(), one_row
 
     # ---- fast path ----------------------------------------------------------------------------------------
+    def _device_suppress_lists(self):
+        """(suppress, blank): the two id lists the token-step kernels take -- SuppressTokens' list plus <|notimestamps|> (the host loops
+        mask it in ApplyTimestampRules), and SuppressBlank's.  Every id is the instance's tokenizer's: 50363 for <|notimestamps|> with 99
+        languages, 50364 with 100."""
+        tk = self.tokenizer
+        suppress = []
+        for f in self.logit_filters:
+            if isinstance(f, SuppressTokens):
+                suppress += list(f.suppress_tokens)
+        if not self.options.without_timestamps and tk.no_timestamps is not None:
+            suppress.append(tk.no_timestamps)
+        blank = list(tk.blank_tokens()) + [tk.eot] if self.options.suppress_blank else []
+        return sorted(set(suppress)), blank
+
     def _fast_state(self, n_batch, device):
         st = self._state.get(n_batch)
         if st is not None:
@@ -305,15 +319,7 @@ class DeviceLoop:
         kv_dtype = torch.int8 if self.use_int8_kv_cache else torch.float16
         if device.type == 'cuda':
             self._check_state_fits(n_batch, device)
-        tk = self.tokenizer
-        suppress = []
-        for f in self.logit_filters:
-            if isinstance(f, SuppressTokens):
-                suppress += list(f.suppress_tokens)
-        if not self.options.without_timestamps and tk.no_timestamps is not None:
-            suppress.append(tk.no_timestamps)
-        suppress = sorted(set(suppress))
-        blank = list(tk.blank_tokens()) + [tk.eot] if self.options.suppress_blank else []
+        suppress, blank = self._device_suppress_lists()
         st = dict(
             kv=[torch.zeros((n_batch, 2, n_head, cap, 64), dtype=kv_dtype, device=device) for _ in range(n_layer)],
             cross=[torch.empty((n_batch // self._cross_group(), 2, n_head, cfg['num_audio_ctx'], 64),

@@ -10,6 +10,7 @@ from __future__ import annotations
 import itertools
 import json
 from collections import OrderedDict
+from pathlib import Path
 
 import torch
 
@@ -39,8 +40,19 @@ def stamp_generation(audio_features):
 class WhisperEncoding:
     def __init__(self, engine_dir, only_torch: bool = False):
         self.dtype = 'float16'
+        with open(Path(engine_dir) / 'encoder_config.json', 'r') as f:
+            builder_config = json.load(f)['builder_config']
+        # the mel bins this engine takes (80: up to large-v2, 128: large-v3 and after): the ONE place the front ends read it from
+        self.num_mels = int(builder_config.get('num_mels', 80))
         if not only_torch:
-            self.session = self.get_session(engine_dir)
+            self.session = self.get_session(Path(engine_dir))
+            assert self.session.dims['n_mels'] == self.num_mels, "encoder_config.json and the engine disagree on num_mels"
+
+    def check_mel(self, mel) -> None:
+        """Refuse a mel whose bin count is not the engine's before the encoder reads it (an 80-bin mel handed to a 128-bin engine would
+        be read past its rows)."""
+        if mel.dim() != 3 or int(mel.shape[1]) != self.num_mels:
+            raise ValueError(f"this engine takes mels of {self.num_mels} bins, [B, {self.num_mels}, frames]; got {tuple(mel.shape)}")
 
     def get_session(self, engine_dir):
         config_path = engine_dir / 'encoder_config.json'
@@ -67,6 +79,7 @@ class WhisperEncoding:
     def get_audio_features(self, mel):
         inputs = OrderedDict()
         output_list = []
+        self.check_mel(mel)
         mel = mel.type(torch.float16).contiguous()
         inputs.update({'x': mel})
         output_list.append(TensorInfo('x', str_dtype_to_trt("float16"), mel.shape))
@@ -89,6 +102,7 @@ class WhisperEncoding:
 
     def get_audio_features_async(self, mel, out=None, cu_budget: int = 0):
         """Fast path: no dictionaries, no synchronisation; enqueued on the current stream."""
+        self.check_mel(mel)
         mel = mel.type(torch.float16).contiguous()
         d = self.session.dims
         if out is None:
@@ -112,6 +126,7 @@ class WhisperEncoding:
     def prefetch(self, mel, cu_budget: int = DEFAULT_SHARED_CU_BUDGET):
         import threading
         assert getattr(self, "_prefetch", None) is None, "one prefetch at a time"
+        self.check_mel(mel)
         if int(mel.shape[0]) < getattr(self, "prefetch_min_batch", PREFETCH_MIN_BATCH):      # (an attribute: tests of the helper path set it to 1)
             # Round 6: batches of up to eight clips are NOT run beside the decode loop -- collect() runs the pass, on the caller's stream.
             # (1) It does not pay there: the loop of such a batch is the one-launch step, which wants every CU for itself (one stage after

@@ -57,6 +57,12 @@ class MelBatch(list):
     def of(cls, mels, content_frames, what: str) -> "MelBatch":
         return mels if isinstance(mels, cls) else cls(mels, content_frames, what)
 
+    def check_bins(self, n_mels: int) -> None:
+        """Refuse a batch whose mels do not have the engine's `n_mels` bins (80 up to large-v2, 128 from large-v3 on)."""
+        for f, m in enumerate(self):
+            if m.dim() != 2 or int(m.shape[0]) != int(n_mels):
+                raise ValueError(f"{self.what}: mel {f} has shape {tuple(m.shape)}, the engine takes mels of {int(n_mels)} bins")
+
     def rows(self):
         """(pointers, row lengths, content frames) as device addresses of int64 [n], int32 [n], int32 [n]: the three arrays every
         mel entry point reads.  The first call validates the batch and uploads the table; later ones return what is there."""

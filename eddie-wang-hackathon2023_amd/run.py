@@ -4,7 +4,8 @@ reference (W/run.py:21-63): prints "transcribe time <s>" and the text.
 Audio front-end: the reference shells out to ffmpeg and computes the log-mel on the GPU with
 torch.stft (W/whisper_utils.py:17-146).  ffmpeg is not on these boxes; `--input_file` accepts a
 `.flac` (wm_flac_decode, csrc/flac_decode.hip -- LibriSpeech's format), a `.wav` (PCM 8 / 16 / 24 / 32
-bit or float32), a `.npy` log-mel `[80, 3000]` or the keyword `synthetic`; a file at another rate than
+bit or float32), a `.npy` log-mel `[num_mels, 3000]` (80 bins up to large-v2, 128 from large-v3 on: the engine's own count, read from
+`WhisperEncoding.num_mels`) or the keyword `synthetic`; a file at another rate than
 16 kHz (4 kHz .. 192 kHz) or with several channels is downmixed and resampled on the device
 (wm_resample, csrc/resample.hip: ffmpeg's `-ar 16000 -ac 1`, with this project's own filter); the log-mel itself is the HIP front end (wm_log_mel, csrc/frontend.hip: STFT + mel +
 log on the device), held to the reference's golden mel in
@@ -47,16 +48,17 @@ def decoding_options(args) -> DecodingOptions:
     return DecodingOptions(beam_size=args.beam_size, patience=args.patience, **logit_controls.options_from_args(args))
 
 
-def load_mel(input_file: str) -> torch.Tensor:
+def load_mel(input_file: str, n_mels: int = 80) -> torch.Tensor:
+    """The fp32 log-mel [n_mels, 3000] of the input; `n_mels`: the engine's (WhisperEncoding.num_mels)."""
     if input_file == 'synthetic':
         import synthetic
-        return synthetic.synthetic_mel(1)[0].float()
+        return synthetic.synthetic_mel(1, n_mels=n_mels)[0].float()
     if input_file.endswith('.npy'):
         return torch.from_numpy(np.load(input_file)).float()
     import whisper_utils
     audio = whisper_utils.pad_or_trim(whisper_utils.load_audio(input_file))
     # STFT + mel projection on the GPU (wm_log_mel); the torch.stft path stays in whisper_utils as the CPU mirror
-    return whisper_utils.log_mel_spectrogram_device(torch.from_numpy(audio).float().cuda(), dtype=torch.float32)
+    return whisper_utils.log_mel_spectrogram_device(torch.from_numpy(audio).float().cuda(), n_mels=n_mels, dtype=torch.float32)
 
 
 def real_mel_frames(input_file: str):
@@ -76,9 +78,9 @@ def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', inpu
     options = decoding_options(argparse.Namespace(**locals()))                  # (the keywords are parse_arguments' names)
     logging.basicConfig(level=getattr(logging, log_level.upper(), logging.ERROR))
     torch.cuda.set_device(0)
-    mel = load_mel(input_file).to('cuda').type(torch.float16).unsqueeze(0)
     engine_dir = Path(engine_dir)
     whisper_encoding = WhisperEncoding(engine_dir)
+    mel = load_mel(input_file, whisper_encoding.num_mels).to('cuda').type(torch.float16).unsqueeze(0)
     whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=options, shared_cross_kv=shared_cross_kv)
     begin_time = time.time()
     audio_features = whisper_encoding.get_audio_features(mel)
@@ -96,6 +98,9 @@ def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', inpu
     return result
 
 
+def main(argv=None):
+    return generate(**vars(parse_arguments(argv)))
+
+
 if __name__ == '__main__':
-    args = parse_arguments()
-    generate(**vars(args))
+    main()

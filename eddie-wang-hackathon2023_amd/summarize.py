@@ -127,12 +127,18 @@ def clean_hypothesis(text: str) -> str:
     return text.translate(str.maketrans({p: "" for p in punctuations})).upper()
 
 
-def mel_batch(audio_list: List[np.ndarray], device) -> torch.Tensor:
-    """fp16 [B, 80, 3000] on `device`: pad_or_trim each clip, STFT + mel projection on the GPU."""
+def mel_batch(audio_list: List[np.ndarray], device, n_mels: int = 80) -> torch.Tensor:
+    """fp16 [B, n_mels, 3000] on `device`: pad_or_trim each clip, STFT + mel projection on the GPU.  `n_mels`: the engine's
+    (WhisperEncoding.num_mels)."""
     padded = np.stack([pad_or_trim(a) for a in audio_list]).astype(np.float32)
     if torch.device(device).type == "cuda":
-        return log_mel_spectrogram_device(torch.from_numpy(padded).to(device), dtype=torch.float16)
-    return torch.stack([log_mel_spectrogram(torch.from_numpy(p)) for p in padded]).half()
+        return log_mel_spectrogram_device(torch.from_numpy(padded).to(device), n_mels=n_mels, dtype=torch.float16)
+    return torch.stack([log_mel_spectrogram(torch.from_numpy(p), n_mels=n_mels) for p in padded]).half()
+
+
+def engine_front_end(whisper_encoding):
+    """`mel_batch` at the engine's own bin count (80 up to large-v2, 128 from large-v3 on): what both dataset loops of main() feed."""
+    return lambda audio_list, device: mel_batch(audio_list, device, whisper_encoding.num_mels)
 
 
 def eval_engines(whisper_encoding, whisper_decoding, mel) -> list:
@@ -193,12 +199,14 @@ def score(hypotheses: List[str], references: List[str], normalizer=None) -> floa
     return word_error_rate([normalizer(t) for t in references], [normalizer(t) for t in hypotheses])
 
 
-def transcribe_dataset_stream(pairs, stream_evaluate, batch_size: int, device) -> Tuple[List[str], List[str], float]:
+def transcribe_dataset_stream(pairs, stream_evaluate, batch_size: int, device, front_end=None) -> Tuple[List[str], List[str], float]:
     """transcribe_dataset for a pipelined evaluator: `stream_evaluate(iterator of mel batches)` yields one result list per
-    batch (eval_engines_stream).  The batches are formed lazily, so the audio of batch n + 1 is read and its log-mel computed
+    batch (eval_engines_stream).  `front_end(audio list, device) -> mel batch`: default `mel_batch` at 80 bins; main() hands in the
+    engine's bin count (`engine_front_end`).  The batches are formed lazily, so the audio of batch n + 1 is read and its log-mel computed
     while batch n decodes; the seconds returned are the wall time of the whole loop (file reading included)."""
     import collections
     hyps, refs, waiting = [], [], collections.deque()
+    front_end = front_end or mel_batch
 
     def batches():
         audio, texts = [], []
@@ -210,11 +218,11 @@ def transcribe_dataset_stream(pairs, stream_evaluate, batch_size: int, device) -
             texts.append(ref)
             if len(audio) == batch_size:
                 waiting.append(list(texts))
-                yield mel_batch(audio, device)
+                yield front_end(audio, device)
                 audio, texts = [], []
         if audio:
             waiting.append(list(texts))
-            yield mel_batch(audio, device)
+            yield front_end(audio, device)
 
     t0 = time.time()
     for results in stream_evaluate(batches()):
@@ -226,17 +234,18 @@ def transcribe_dataset_stream(pairs, stream_evaluate, batch_size: int, device) -
     return hyps, refs, time.time() - t0
 
 
-def transcribe_dataset(pairs, evaluate, batch_size: int, device) -> Tuple[List[str], List[str], float]:
+def transcribe_dataset(pairs, evaluate, batch_size: int, device, front_end=None) -> Tuple[List[str], List[str], float]:
     """Run `evaluate(mel) -> [DecodingResult]` over the clips that fit 30 s; returns (hypotheses, references,
-    seconds spent in `evaluate`)."""
+    seconds spent in `evaluate`).  `front_end(audio list, device) -> mel batch`: default `mel_batch` at 80 bins."""
     hyps, refs, batch_audio, batch_refs = [], [], [], []
+    front_end = front_end or mel_batch
     elapsed = 0.0
 
     def flush():
         nonlocal elapsed
         if not batch_audio:
             return
-        mel = mel_batch(batch_audio, device)
+        mel = front_end(batch_audio, device)
         torch.cuda.synchronize() if mel.is_cuda else None
         t0 = time.time()
         results = evaluate(mel)
@@ -313,9 +322,10 @@ def main(args) -> Optional[dict]:
     for name, evaluate in runs:
         if name == "whisper-mi355" and args.overlap_encoder:
             hyps, refs, seconds = transcribe_dataset_stream(
-                mine, lambda mels: eval_engines_stream(whisper_encoding, whisper_decoding, mels), args.batch_size, device)
+                mine, lambda mels: eval_engines_stream(whisper_encoding, whisper_decoding, mels), args.batch_size, device,
+                engine_front_end(whisper_encoding))
         else:
-            hyps, refs, seconds = transcribe_dataset(mine, evaluate, args.batch_size, device)
+            hyps, refs, seconds = transcribe_dataset(mine, evaluate, args.batch_size, device, engine_front_end(whisper_encoding))
         hyps, refs, seconds = gather_transcripts(hyps, refs, seconds)
         if rank == 0:
             value = score(hyps, refs)

@@ -32,6 +32,16 @@ DIMS = {
                   n_vocab=1024, n_text_ctx=32, n_text_state=128, n_text_head=2, n_text_layer=2),
     "micro-fullvocab": dict(n_mels=80, n_audio_ctx=64, n_audio_state=128, n_audio_head=2, n_audio_layer=2,
                             n_vocab=51865, n_text_ctx=448, n_text_state=128, n_text_head=2, n_text_layer=2),
+    # the large-v3 generation: 128 mel bins, 100 languages (51866 tokens); turbo and distil keep the encoder and cut the decoder
+    "large-v3": dict(n_mels=128, n_audio_ctx=1500, n_audio_state=1280, n_audio_head=20, n_audio_layer=32,
+                     n_vocab=51866, n_text_ctx=448, n_text_state=1280, n_text_head=20, n_text_layer=32),
+    "large-v3-turbo": dict(n_mels=128, n_audio_ctx=1500, n_audio_state=1280, n_audio_head=20, n_audio_layer=32,
+                           n_vocab=51866, n_text_ctx=448, n_text_state=1280, n_text_head=20, n_text_layer=4),
+    "distil-large-v3": dict(n_mels=128, n_audio_ctx=1500, n_audio_state=1280, n_audio_head=20, n_audio_layer=32,
+                            n_vocab=51866, n_text_ctx=448, n_text_state=1280, n_text_head=20, n_text_layer=2),
+    # the v3 layout at test size: 128 bins, the whole 51866-token vocabulary, and unequal depths on purpose (2 encoder, 1 decoder layer)
+    "micro-v3": dict(n_mels=128, n_audio_ctx=64, n_audio_state=128, n_audio_head=2, n_audio_layer=2,
+                     n_vocab=51866, n_text_ctx=448, n_text_state=128, n_text_head=2, n_text_layer=1),
 }
 
 

@@ -148,7 +148,9 @@ def words_from_path(text_indices, time_indices, words: Sequence[str], word_token
 
 
 def default_alignment_heads(n_text_layer: int, n_text_head: int) -> List[int]:
-    """Upstream's default: every head of the upper half of the decoder layers, as layer * n_text_head + head, ascending."""
+    """Upstream's default: every head of the upper half of the decoder layers, as layer * n_text_head + head, ascending (32 layers:
+    16 .. 31; large-v3-turbo's 4: 2 and 3; one layer: layer 0).  Upstream ships measured per-model heads for its released checkpoints
+    (large-v3 and turbo among them) as data this project does not have: `build.py --alignment_heads` is the way to supply them."""
     return [l * n_text_head + h for l in range(n_text_layer // 2, n_text_layer) for h in range(n_text_head)]
 
 

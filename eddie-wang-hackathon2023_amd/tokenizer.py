@@ -11,6 +11,9 @@ The reference delegates BPE to the `tiktoken` wheel (absent here, no network).  
 implements byte-pair merging itself, in the published tiktoken order: split with the GPT-2
 pattern, then repeatedly merge the adjacent pair with the lowest rank.
 
+Two layouts: `num_languages` = 99 (up to large-v2; the default) or 100 (large-v3 and after: <|yue|> follows <|su|> and every special
+behind the language block is one id higher; same BPE ranks).  `layout_from_vocab` derives it from a model's vocabulary size.
+
 Two modes:
 * vocabulary mode  -- `Tokenizer.from_vocab(path_to_*.tiktoken, ...)`: everything works.
 * ids-only mode    -- `Tokenizer.ids_only(multilingual=True)`: no vocabulary file on the box
@@ -25,12 +28,13 @@ from dataclasses import dataclass, field
 from functools import cached_property
 from typing import Dict, List, Optional, Sequence, Tuple
 
-# ISO codes in Whisper's language-token order (data; order defines ids sot+1 ... sot+99)
+# ISO codes in Whisper's language-token order (data; order defines ids sot+1 ... sot+100).  The first 99 are the large-v2
+# generation's; large-v3 appended Cantonese, so a tokenizer takes the first `num_languages` (99 or 100) of them
 LANGUAGE_CODES: Tuple[str, ...] = tuple(
     "en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk el ms cs ro da hu ta no "
     "th ur hr bg lt la mi ml cy sk te fa lv bn sr az sl kn et mk br eu is hy ne mn bs kk sq sw "
     "gl mr pa si km sn yo so af oc ka be tg sd gu am yi lo uz fo ht ps tk nn mt sa lb my bo tl "
-    "mg as tt haw ln ha ba jw su".split())
+    "mg as tt haw ln ha ba jw su yue".split())
 LANGUAGE_NAMES: Tuple[str, ...] = tuple(
     "english chinese german spanish russian korean french japanese portuguese turkish polish "
     "catalan dutch arabic swedish italian indonesian hindi finnish vietnamese hebrew ukrainian "
@@ -41,15 +45,41 @@ LANGUAGE_NAMES: Tuple[str, ...] = tuple(
     "yoruba somali afrikaans occitan georgian belarusian tajik sindhi gujarati amharic yiddish "
     "lao uzbek faroese haitian_creole pashto turkmen nynorsk maltese sanskrit luxembourgish "
     "myanmar tibetan tagalog malagasy assamese tatar hawaiian lingala hausa bashkir javanese "
-    "sundanese".split())
+    "sundanese cantonese".split())
 LANGUAGES: Dict[str, str] = {c: n.replace("_", " ") for c, n in zip(LANGUAGE_CODES, LANGUAGE_NAMES)}
 TO_LANGUAGE_CODE: Dict[str, str] = {
     **{n: c for c, n in LANGUAGES.items()},
     "burmese": "my", "valencian": "ca", "flemish": "nl", "haitian": "ht", "letzeburgesch": "lb",
     "pushto": "ps", "panjabi": "pa", "moldavian": "ro", "moldovan": "ro", "sinhalese": "si",
-    "castilian": "es",
+    "castilian": "es", "mandarin": "zh",
 }
-assert len(LANGUAGE_CODES) == len(LANGUAGE_NAMES) == 99
+NUM_LANGUAGES = (99, 100)      # large-v2 and before / large-v3 and after
+assert len(LANGUAGE_CODES) == len(LANGUAGE_NAMES) == max(NUM_LANGUAGES)
+N_TIMESTAMPS = 1501
+
+
+def layout_from_vocab(n_vocab: int) -> Tuple[bool, int]:
+    """(multilingual, num_languages) of a model with `n_vocab` tokens: what everything that builds a tokenizer from a config uses.
+    Upstream's rule: multilingual = n_vocab >= 51865, num_languages = n_vocab - 51765 - int(multilingual) -- 51864 -> English-only / 99,
+    51865 -> 99, 51866 -> 100.  A size the rule turns into anything but 99 or 100 is refused: decoding it with some other generation's
+    ids would be silently wrong.  A vocabulary below 51864 tokens holds no special token at all (the `micro` test models: 1024 tokens,
+    raw logits only); it keeps the English-only, 99-language ids it always had."""
+    n_vocab = int(n_vocab)
+    if n_vocab < 51864:
+        return False, 99
+    multilingual = n_vocab >= 51865
+    n = n_vocab - 51765 - int(multilingual)
+    if n not in NUM_LANGUAGES:
+        raise ValueError(f"vocabulary of {n_vocab} tokens: the rule n_vocab - 51765 - int(multilingual) gives {n} languages, known are "
+                         f"{NUM_LANGUAGES} (51864 / 51865 / 51866 tokens)")
+    return multilingual, n
+
+
+def check_num_languages(num_languages: int) -> int:
+    if num_languages not in NUM_LANGUAGES:
+        raise ValueError(f"num_languages must be one of {NUM_LANGUAGES}, got {num_languages}")
+    return int(num_languages)
+
 
 GPT2_SPLIT = r"""'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"""
 
@@ -116,11 +146,12 @@ class BPE:
         return b"".join(self.by_rank[i] for i in ids)
 
 
-def special_token_table(n_base: int) -> Dict[str, int]:
-    """Specials appended after the BPE ranks in the reference's order (W/decoding.py:433-449)."""
-    names = ["<|endoftext|>", "<|startoftranscript|>", *[f"<|{c}|>" for c in LANGUAGE_CODES],
+def special_token_table(n_base: int, num_languages: int = 99) -> Dict[str, int]:
+    """Specials appended after the BPE ranks in the reference's order (W/decoding.py:433-449); with 100 languages <|yue|> follows
+    <|su|> and every special behind the language block is one id higher (upstream Whisper's large-v3 layout)."""
+    names = ["<|endoftext|>", "<|startoftranscript|>", *[f"<|{c}|>" for c in LANGUAGE_CODES[:check_num_languages(num_languages)]],
              "<|translate|>", "<|transcribe|>", "<|startoflm|>", "<|startofprev|>",
-             "<|nospeech|>", "<|notimestamps|>", *[f"<|{i * 0.02:.2f}|>" for i in range(1501)]]
+             "<|nospeech|>", "<|notimestamps|>", *[f"<|{i * 0.02:.2f}|>" for i in range(N_TIMESTAMPS)]]
     return {n: n_base + i for i, n in enumerate(names)}
 
 
@@ -132,13 +163,16 @@ class Tokenizer:
     bpe: Optional[BPE] = None
     special_tokens: Dict[str, int] = field(default_factory=dict)
     sot_sequence: Tuple[int, ...] = ()
+    num_languages: int = 99                      # 99: large-v2 and before / 100: large-v3 and after (<|yue|>)
 
     def __post_init__(self):
-        self.special_tokens = special_token_table(self.n_base)
+        self.special_tokens = special_token_table(self.n_base, self.num_languages)
         self._special_by_id = {v: k for k, v in self.special_tokens.items()}
         seq = [self.sot]
         if self.language is not None:
-            seq.append(self.sot + 1 + LANGUAGE_CODES.index(self.language))
+            if self.language not in self.all_language_codes:
+                raise ValueError(f"Unsupported language: {self.language} (this vocabulary has {self.num_languages} languages)")
+            seq.append(self.sot + 1 + self.all_language_codes.index(self.language))
         if self.task is not None:
             seq.append(self.transcribe if self.task == "transcribe" else self.translate)
         self.sot_sequence = tuple(seq)
@@ -146,27 +180,24 @@ class Tokenizer:
     # -- constructors ------------------------------------------------------------------
     @classmethod
     def from_vocab(cls, path: str, multilingual: bool = True, language: Optional[str] = None,
-                   task: Optional[str] = None) -> "Tokenizer":
+                   task: Optional[str] = None, num_languages: int = 99) -> "Tokenizer":
         bpe = BPE.from_file(path)
-        language, task = cls._defaults(multilingual, language, task)
-        return cls(n_base=len(bpe.ranks), language=language, task=task, bpe=bpe)
+        language, task = cls._defaults(multilingual, language, task, num_languages)
+        return cls(n_base=len(bpe.ranks), language=language, task=task, bpe=bpe, num_languages=num_languages)
 
     @classmethod
     def ids_only(cls, multilingual: bool = True, language: Optional[str] = None,
-                 task: Optional[str] = None) -> "Tokenizer":
-        language, task = cls._defaults(multilingual, language, task)
-        return cls(n_base=50257 if multilingual else 50256, language=language, task=task)
+                 task: Optional[str] = None, num_languages: int = 99) -> "Tokenizer":
+        language, task = cls._defaults(multilingual, language, task, num_languages)
+        return cls(n_base=50257 if multilingual else 50256, language=language, task=task, num_languages=num_languages)
 
     @staticmethod
-    def _defaults(multilingual, language, task):
-        # W/decoding.py:458-481
+    def _defaults(multilingual, language, task, num_languages: int = 99):
+        # W/decoding.py:458-481; a name or code of a language the vocabulary has no token for (yue at 99) is refused like an unknown one
         if language is not None:
-            language = language.lower()
-            if language not in LANGUAGES:
-                if language in TO_LANGUAGE_CODE:
-                    language = TO_LANGUAGE_CODE[language]
-                else:
-                    raise ValueError(f"Unsupported language: {language}")
+            language = TO_LANGUAGE_CODE.get(language.lower(), language.lower())
+            if language not in LANGUAGE_CODES[:check_num_languages(num_languages)]:
+                raise ValueError(f"Unsupported language: {language}")
         if multilingual:
             return language or "en", task or "transcribe"
         return None, None
@@ -201,11 +232,11 @@ class Tokenizer:
 
     @cached_property
     def all_language_tokens(self) -> Tuple[int, ...]:
-        return tuple(self.special_tokens[f"<|{c}|>"] for c in LANGUAGE_CODES)
+        return tuple(self.special_tokens[f"<|{c}|>"] for c in self.all_language_codes)
 
-    @cached_property
+    @property
     def all_language_codes(self) -> Tuple[str, ...]:
-        return LANGUAGE_CODES
+        return LANGUAGE_CODES[:self.num_languages]
 
     @cached_property
     def sot_sequence_including_notimestamps(self) -> Tuple[int, ...]:

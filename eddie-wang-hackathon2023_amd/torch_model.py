@@ -132,6 +132,12 @@ class Whisper:
     def is_multilingual(self) -> bool:
         return self.dims.n_vocab >= 51865
 
+    @property
+    def num_languages(self) -> int:
+        """99 (up to large-v2) or 100 (large-v3 and after), from the vocabulary size (upstream's `Whisper.num_languages`)."""
+        from tokenizer import layout_from_vocab
+        return layout_from_vocab(self.dims.n_vocab)[1]
+
     def parameters(self) -> Iterable[Tensor]:
         return self.p.values()
 

@@ -14,6 +14,10 @@ longform.py states the contract (the rules and the schedule, on the host, tested
     kernel closes them with EOT at the first step and the attention kernels drop them -- because a change of batch size makes
     WhisperDecoding free and re-allocate its whole buffer set and its graphs;
   * a file's language is detected on its first window (unless the options name one) and kept for all of its windows.
+  * the engine says what it is fed and how its tokens are numbered: the log-mels are computed at `WhisperEncoding.num_mels` bins
+    (80 up to large-v2, 128 for large-v3 / large-v3-turbo / distil-large-v3) and a mel of another bin count is refused before a
+    kernel reads it (MelBatch.check_bins); the languages and every special id are the decoder's tokenizer's (99 languages up to
+    large-v2, 100 with `yue` from large-v3 on: tokenizer.layout_from_vocab); `--language yue` on a 99-language engine is refused.
 
   * `condition_on_previous_text` / `initial_prompt` (upstream's options; default here: off -- upstream's default is on): every
     file carries its own history (longform.PromptHistory), a round hands the decoder one prompt per row
@@ -235,6 +239,8 @@ def _transcribe_layers(encoding, decoding, batch: MelBatch, W: int, fs: float, k
     back, innermost first.  `channels`: (ChannelOptions, channel_counts, the downmixes' batch or None)."""
     if len(batch) == 0:
         return []
+    if encoding is not None:            # (the engine's bin count, before any kernel reads a mel; without an encoder there is none to hold them to)
+        batch.check_bins(encoding.num_mels)
     joins, owner = [], None
     if channels is not None:
         batch, join = _split_channels(batch, W, fs, *channels)
@@ -312,7 +318,7 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
 
 def _named_language(decoding: WhisperDecoding) -> Optional[str]:
     if decoding.is_multilingual and decoding.options.language is not None:
-        return Tokenizer._defaults(True, decoding.options.language, None)[0]
+        return Tokenizer._defaults(True, decoding.options.language, None, decoding.tokenizer.num_languages)[0]
     return None
 
 
@@ -344,6 +350,7 @@ def _transcribe_files(encoding: WhisperEncoding, decoding: WhisperDecoding, mels
     if n_files == 0:
         return []
     n_mels, dev = mels.n_mels, mels.device
+    mels.check_bins(encoding.num_mels)
     for f, (m, c) in enumerate(zip(mels, content_frames)):
         if m.dim() != 2 or m.shape[0] != n_mels or m.shape[1] < c or c < 0:
             raise ValueError(f"transcribe: mel {f} has shape {tuple(m.shape)} for {c} frames of content")
@@ -450,12 +457,12 @@ def _transcribe_recordings(encoding, decoding, audio_or_paths, options: ChannelO
         wave = wu.load_audio_device(str(a), channels="split")
         mono = wu.load_audio_device(str(a)) if options.mode == "label" else None
         for c in range(wave.shape[0]):
-            mel, frames = wu.long_log_mel_device(wave[c].contiguous())
+            mel, frames = wu.long_log_mel_device(wave[c].contiguous(), n_mels=encoding.num_mels)
             mels.append(mel)
             content.append(frames)
         counts.append(int(wave.shape[0]))
         if mono is not None:
-            mel, frames = wu.long_log_mel_device(mono.float().flatten())
+            mel, frames = wu.long_log_mel_device(mono.float().flatten(), n_mels=encoding.num_mels)
             mono_mels.append(mel)
             mono_content.append(frames)
     batch, W, fs = _batch(decoding, mels, content, own=options.bleed_db is not None)      # (and its batch, once they are)
@@ -478,7 +485,7 @@ def transcribe(encoding: WhisperEncoding, decoding: WhisperDecoding, audio_or_pa
         if isinstance(a, (str, Path)):
             a = wu.load_audio_device(str(a))
         a = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a, dtype=np.float32))
-        mel, frames = wu.long_log_mel_device(a.float().flatten().cuda())
+        mel, frames = wu.long_log_mel_device(a.float().flatten().cuda(), n_mels=encoding.num_mels)
         mels.append(mel)
         content.append(frames)
     return transcribe_mel(encoding, decoding, mels, content, **kw)
@@ -495,7 +502,9 @@ def parse_arguments(argv=None):
     parser.add_argument('--engine_dir', type=str, default='whisper_outputs')
     parser.add_argument('--input_file', type=str, nargs='+', required=True, help='.flac / .wav files of any length, 4 kHz .. 192 kHz, any channel count (resampled to 16 kHz mono on the GPU)')
     parser.add_argument('--vocab', type=str, default=None, help='path to multilingual.tiktoken (text output)')
-    parser.add_argument('--language', type=str, default=None, help='language of the files (default: detected per file)')
+    parser.add_argument('--language', type=str, default=None,
+                        help="language of the files, a code or a name of the engine's vocabulary (default: detected per file; yue / "
+                             "cantonese only with a 100-language engine: large-v3 and after)")
     parser.add_argument('--temperature', type=float, nargs='+', default=list(longform.TEMPERATURES),
                         help='the fallback ladder (default: 0 0.2 0.4 0.6 0.8 1)')
     parser.add_argument('--no_fallback', default=False, action='store_true', help='decode every window once, at the first temperature')

@@ -218,7 +218,8 @@ def _qkv(params, prefix):
 
 def conv_weight_as_gemm(w: np.ndarray) -> np.ndarray:
     """Conv1d weight [C_out, C_in, 3] -> the GEMM matrix [C_out, K] the engine multiplies token-major rows with:
-    K index = tap * C_in + c_in, zero columns up to a multiple of 64 (the GEMM's K tile)."""
+    K index = tap * C_in + c_in, zero columns up to a multiple of 64 (the GEMM's K tile): 80 bins give 240 -> 256, 128 bins give 384 and
+    nothing is appended."""
     c_out, c_in, taps = w.shape
     g = np.asarray(w, dtype=np.float16).transpose(0, 2, 1).reshape(c_out, taps * c_in)
     kpad = (taps * c_in + 63) // 64 * 64
@@ -231,7 +232,7 @@ def load_encoder_weight(model_metadata: dict, model_params: dict, n_layer: int,
     t: "OrderedDict[str, np.ndarray]" = OrderedDict()
     C, n_mels = model_metadata["n_audio_state"], model_metadata["n_mels"]
     # convolutions as GEMMs over token-major rows: K index = tap * C_in + c_in
-    t["conv1.w"] = conv_weight_as_gemm(_np(model_params["encoder.conv1.weight"]))      # [C, n_mels, 3] -> [C, 256]
+    t["conv1.w"] = conv_weight_as_gemm(_np(model_params["encoder.conv1.weight"]))      # [C, n_mels, 3] -> [C, 256] (80 bins) / [C, 384] (128 bins)
     t["conv1.b"] = _np(model_params["encoder.conv1.bias"]).astype(np.float16)
     t["conv2.w"] = conv_weight_as_gemm(_np(model_params["encoder.conv2.weight"]))      # [C, C, 3] -> [C, 3C]
     t["conv2.b"] = _np(model_params["encoder.conv2.bias"]).astype(np.float16)

@@ -8,7 +8,9 @@ state it on the host in fp64, `resample_device` runs it on the GPU (wm_resample,
 in one launch).  The filter is this project's design, not swresample's: outputs differ from ffmpeg's in the last bits and in the
 transition band.  The 80x201 mel filterbank is regenerated with the recipe the reference quotes
 (`librosa.filters.mel(sr=16000, n_fft=400, n_mels=80)`, W/whisper_utils.py:85-90: Slaney scale, Slaney area normalisation)
-instead of shipping the `.npz`; tests/golden/mel.npz (made with the reference's own function and asset) pins both.  The STFT of
+instead of shipping the `.npz`; tests/golden/mel.npz (made with the reference's own function and asset) pins both.  The same
+recipe with n_mels=128 gives the 128x201 bank of large-v3 and after (upstream's `mel_128`); `mel_filters` takes 80 or 128 and
+every caller passes its engine's `num_mels`.  The STFT of
 `log_mel_spectrogram` runs through torch on whatever device the audio is on; `log_mel_spectrogram_device` is the HIP kernel.
 """
 from __future__ import annotations
@@ -364,7 +366,9 @@ def _mel_filterbank(n_mels: int = N_MELS, n_fft: int = N_FFT, sr: int = SAMPLE_R
 
 
 def mel_filters(device, n_mels: int = N_MELS) -> torch.Tensor:
-    assert n_mels == 80, f"Unsupported n_mels: {n_mels}"
+    """[n_mels, 201] fp32: 80 bins (Whisper up to large-v2) or 128 (large-v3 and after), the two banks upstream ships."""
+    if n_mels not in (80, 128):
+        raise ValueError(f"Unsupported n_mels: {n_mels} (Whisper models take 80 or 128 mel bins)")
     return torch.from_numpy(_mel_filterbank(n_mels)).to(device)
 
 
