@@ -13,6 +13,8 @@
 // No atomics, a fixed order of every sum: the result is deterministic.
 //   dtw_kernel        one workgroup per utterance walks the anti-diagonals (the last three in LDS, one barrier each, trace bytes in
 //                     the workspace), then walks back and writes the reversed path.
+// Forced alignment (its host form alignment.py) adds the open end of that walk (wm_dtw_open, wm_align_open: the same
+// kernel, templated) and the tap of a whole block (tap_q_block_kernel behind wm_decoder_prefill_tap).
 #include "decode_math.h"
 #include "kernels.h"
 #include "../../include/whisper_mi355.h"
@@ -55,6 +57,28 @@ __global__ __launch_bounds__(64) void tap_q_kernel(const float* part, int ksplit
     }
     const float bs = bias ? (float)bias[col] : 0.f;
     tape[(((size_t)b * n_tape_heads + tl.slot[hi]) * capacity + T + l) * 64 + d] = (h16)(qa + bs);
+}
+
+// The same for a whole block (wm_decoder_prefill_tap): the slabs added in attn_prefill.hip's order (slab_row8: rounds of four, then a
+// tail one by one), the row index folded over blockIdx.y and .z (a block of 224 tokens x 576 rows passes 65 535)
+__global__ __launch_bounds__(64) void tap_q_block_kernel(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int L, int n_rows,
+                                                         h16* tape, int n_tape_heads, int capacity, TapLayer tl) {
+    const int d = threadIdx.x, hi = blockIdx.x;
+    const long row = (long)blockIdx.z * gridDim.y + blockIdx.y;
+    if (row >= n_rows) return;
+    const int b = (int)(row / L), l = (int)(row - (long)b * L);
+    const int col = (int)tl.head[hi] * 64 + d;
+    const float* src = part + (size_t)row * ldp + col;
+    float qa = 0.f;
+    int s = 0;
+    for (; s + 4 <= ksplit; s += 4) {
+        const float x0 = src[(size_t)s * sstride], x1 = src[(size_t)(s + 1) * sstride];
+        const float x2 = src[(size_t)(s + 2) * sstride], x3 = src[(size_t)(s + 3) * sstride];
+        qa += (x0 + x1) + (x2 + x3);
+    }
+    for (; s < ksplit; ++s) qa += src[(size_t)s * sstride];
+    const float bs = bias ? (float)bias[col] : 0.f;
+    tape[(((size_t)b * n_tape_heads + tl.slot[hi]) * capacity + l) * 64 + d] = (h16)(qa + bs);
 }
 
 // ---- the alignment matrix -----------------------------------------------------------------------------------------------------------
@@ -263,14 +287,26 @@ struct DtwParams {
     unsigned char* trace;                                // [batch][max_rows + 1][max_cols + 1]
 };
 
-// thread i owns row i of the cost table; on diagonal d it computes cell (i, d - i) from the two diagonals before
-__global__ __launch_bounds__(1024) void dtw_kernel(DtwParams p) {
+// thread i owns row i of the cost table; on diagonal d it computes cell (i, d - i) from the two diagonals before.
+// OPEN (wm_dtw_open, wm_align_open): the walk back starts at (i*, M), i* the smallest row whose cost in the last column is the
+// column's minimum -- thread i keeps cost[i][M] from diagonal i + M in a register, a wave reduces (value, row) by shuffles and
+// thread 0 reduces the waves' results from LDS: no second pass over the table.  Everything OPEN adds sits under `if constexpr`,
+// and the closed instantiation takes DtwParams alone, so it is the kernel it was, argument layout included.
+struct DtwOpenParams : DtwParams { int* end_row; };
+template <bool OPEN> struct DtwArg { using type = DtwParams; };
+template <> struct DtwArg<true> { using type = DtwOpenParams; };
+
+template <bool OPEN>
+__global__ __launch_bounds__(1024) void dtw_kernel(typename DtwArg<OPEN>::type p) {
     extern __shared__ float dl[];
     __shared__ int s_len;
     const int b = blockIdx.x, tid = threadIdx.x, i = tid;
     const int N = min(p.n_rows[b], p.max_rows) - p.row_sub, M = min(p.n_cols[b], p.max_cols);      // (the clip of the matrix kernels, then the cut rows)
     if (N < 1 || M < 1) {
-        if (tid == 0) p.path_len[b] = 0;
+        if (tid == 0) {
+            p.path_len[b] = 0;
+            if constexpr (OPEN) p.end_row[b] = 0;
+        }
         return;
     }
     const int R = p.max_rows + 1, TS = p.max_cols + 1;
@@ -281,6 +317,7 @@ __global__ __launch_bounds__(1024) void dtw_kernel(DtwParams p) {
     const float* xrow = x + (size_t)(i > 0 ? i - 1 : 0) * p.ldx;
     // x of this thread's cell on the NEXT diagonal is requested while the current one is computed
     float x_next = 0.f;
+    [[maybe_unused]] float last = INFINITY;              // (OPEN) cost[i][M]
     for (int d = 0; d <= N + M; ++d) {
         float* cur = dl + (d % 3) * R;
         const float* prev1 = dl + ((d + 2) % 3) * R;
@@ -302,13 +339,36 @@ __global__ __launch_bounds__(1024) void dtw_kernel(DtwParams p) {
                 tr[(size_t)i * TS + j] = t;
             }
             cur[i] = v;
+            if constexpr (OPEN) {
+                if (i >= 1 && j == M) last = v;
+            }
         }
         __syncthreads();
+    }
+    [[maybe_unused]] int start_row = N;
+    if constexpr (OPEN) {
+        __shared__ float s_best[16];
+        __shared__ int s_row[16];
+        float bv = last; int bi = (i >= 1 && i <= N) ? i : 0x7fffffff;
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const float ov = __shfl_xor(bv, m); const int oi = __shfl_xor(bi, m);
+            if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if ((tid & 63) == 0) { s_best[tid >> 6] = bv; s_row[tid >> 6] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            const int n_waves = (int)blockDim.x >> 6;
+            for (int k = 1; k < n_waves; ++k)
+                if (s_best[k] < bv || (s_best[k] == bv && s_row[k] < bi)) { bv = s_best[k]; bi = s_row[k]; }
+            start_row = (bi >= 1 && bi <= N) ? bi : 1;   // (NaN or +inf everywhere: row 1, the first candidate)
+            p.end_row[b] = start_row;
+        }
     }
     __threadfence();
     __syncthreads();
     if (tid == 0) {
-        int a = N, c = M, n = 0;
+        int a = OPEN ? start_row : N, c = M, n = 0;
         while ((a > 0 || c > 0) && n < P) {
             rev[n] = a - 1; rev[P + n] = c - 1; ++n;
             const int t = a == 0 ? 2 : (c == 0 ? 1 : (int)tr[(size_t)a * TS + c]);
@@ -335,12 +395,19 @@ DtwWs carve_dtw(int batch, int max_rows, int max_cols) {
     return w;
 }
 
-int launch_dtw(DtwParams p, int batch, hipStream_t s) {
+int launch_dtw(DtwParams p, int batch, hipStream_t s, int* end_row = nullptr) {
     WM_REQUIRE(p.max_rows >= 1 && p.max_rows <= 1023 && p.max_cols >= 1, "dtw: max_rows %d must be in 1 .. 1023, max_cols %d >= 1", p.max_rows, p.max_cols);
     const size_t lds = (size_t)3 * (p.max_rows + 1) * sizeof(float) + (size_t)2 * (p.max_rows + p.max_cols) * sizeof(int);
     WM_REQUIRE(lds <= 60 * 1024, "dtw: %d rows x %d columns need %zu bytes of LDS", p.max_rows, p.max_cols, lds);
     const int threads = p.max_rows + 1 <= 512 ? 512 : 1024;
-    hipLaunchKernelGGL(dtw_kernel, dim3(batch), dim3(threads), lds, s, p);
+    if (end_row) {
+        DtwOpenParams po{};
+        static_cast<DtwParams&>(po) = p;
+        po.end_row = end_row;
+        hipLaunchKernelGGL(dtw_kernel<true>, dim3(batch), dim3(threads), lds, s, po);
+    } else {
+        hipLaunchKernelGGL(dtw_kernel<false>, dim3(batch), dim3(threads), lds, s, p);
+    }
     WM_LAUNCH_CHECK(s, "dtw");
     return 0;
 }
@@ -373,6 +440,20 @@ int launch_tap_q(const float* part, int ksplit, int ldp, long sstride, const h16
     return 0;
 }
 
+int launch_tap_q_block(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, h16* tape, int n_tape_heads,
+                       int capacity, const int* heads_in_layer, const int* slots, int n, hipStream_t s) {
+    WM_REQUIRE(n >= 1 && n <= 64, "tap: %d heads in one layer", n);
+    WM_REQUIRE(B >= 1 && L >= 1 && L <= capacity && (long)B * L <= 0x7fffffffL, "tap: bad block (%d rows x %d tokens, capacity %d)", B, L, capacity);
+    TapLayer tl{};
+    tl.n = n;
+    for (int k = 0; k < n; ++k) { tl.head[k] = (unsigned char)heads_in_layer[k]; tl.slot[k] = (short)slots[k]; }
+    const int n_rows = B * L, gy = n_rows < 65535 ? n_rows : 65535, gz = (n_rows + gy - 1) / gy;
+    WM_REQUIRE(gz <= 65535, "tap: %d rows", n_rows);
+    hipLaunchKernelGGL(tap_q_block_kernel, dim3(n, gy, gz), dim3(64), 0, s, part, ksplit, ldp, sstride, bias, L, n_rows, tape, n_tape_heads, capacity, tl);
+    WM_LAUNCH_CHECK(s, "tap_q_block");
+    return 0;
+}
+
 }  // namespace wm
 
 using namespace wm;
@@ -384,20 +465,36 @@ size_t wm_dtw_workspace_bytes(int batch, int max_rows, int max_cols) {
     return carve_dtw(batch, max_rows, max_cols).total;
 }
 
-int wm_dtw(const float* x, int ldx, int64_t x_bstride, int batch, const int32_t* n_rows, const int32_t* n_cols, int max_rows,
-           int max_cols, int32_t* path_text, int32_t* path_time, int path_ld, int32_t* path_len, void* workspace,
-           size_t workspace_bytes, wm_stream_t stream) {
-    WM_REQUIRE(x && n_rows && n_cols && path_text && path_time && path_len && workspace, "wm_dtw: null argument");
-    WM_REQUIRE(batch >= 1 && ldx >= max_cols && path_ld >= 1, "wm_dtw: bad batch / ldx / path_ld (%d, %d, %d)", batch, ldx, path_ld);
-    WM_REQUIRE(max_rows >= 1 && max_cols >= 1, "wm_dtw: bad max_rows / max_cols (%d, %d)", max_rows, max_cols);
-    WM_REQUIRE(workspace_bytes >= wm_dtw_workspace_bytes(batch, max_rows, max_cols), "wm_dtw: workspace too small: %zu < %zu",
+// wm_dtw (end_row == null) and wm_dtw_open
+static int dtw_entry(const char* who, const float* x, int ldx, int64_t x_bstride, int batch, const int32_t* n_rows, const int32_t* n_cols,
+                     int max_rows, int max_cols, int32_t* path_text, int32_t* path_time, int path_ld, int32_t* path_len, int32_t* end_row,
+                     void* workspace, size_t workspace_bytes, wm_stream_t stream) {
+    WM_REQUIRE(x && n_rows && n_cols && path_text && path_time && path_len && workspace, "%s: null argument", who);
+    WM_REQUIRE(batch >= 1 && ldx >= max_cols && path_ld >= 1, "%s: bad batch / ldx / path_ld (%d, %d, %d)", who, batch, ldx, path_ld);
+    WM_REQUIRE(max_rows >= 1 && max_cols >= 1, "%s: bad max_rows / max_cols (%d, %d)", who, max_rows, max_cols);
+    WM_REQUIRE(workspace_bytes >= wm_dtw_workspace_bytes(batch, max_rows, max_cols), "%s: workspace too small: %zu < %zu", who,
                workspace_bytes, wm_dtw_workspace_bytes(batch, max_rows, max_cols));
     DtwParams p{};
     p.x = x; p.ldx = ldx; p.x_bstride = (long)x_bstride; p.negate = 0;
     p.n_rows = n_rows; p.row_sub = 0; p.n_cols = n_cols; p.max_rows = max_rows; p.max_cols = max_cols;
     p.path_text = path_text; p.path_time = path_time; p.path_ld = path_ld; p.path_len = path_len;
     p.trace = (unsigned char*)workspace;
-    return launch_dtw(p, batch, (hipStream_t)stream);
+    return launch_dtw(p, batch, (hipStream_t)stream, end_row);
+}
+
+int wm_dtw(const float* x, int ldx, int64_t x_bstride, int batch, const int32_t* n_rows, const int32_t* n_cols, int max_rows,
+           int max_cols, int32_t* path_text, int32_t* path_time, int path_ld, int32_t* path_len, void* workspace,
+           size_t workspace_bytes, wm_stream_t stream) {
+    return dtw_entry("wm_dtw", x, ldx, x_bstride, batch, n_rows, n_cols, max_rows, max_cols, path_text, path_time, path_ld, path_len,
+                     nullptr, workspace, workspace_bytes, stream);
+}
+
+int wm_dtw_open(const float* x, int ldx, int64_t x_bstride, int batch, const int32_t* n_rows, const int32_t* n_cols, int max_rows,
+                int max_cols, int32_t* path_text, int32_t* path_time, int path_ld, int32_t* path_len, int32_t* end_row, void* workspace,
+                size_t workspace_bytes, wm_stream_t stream) {
+    WM_REQUIRE(end_row, "wm_dtw_open: null argument");
+    return dtw_entry("wm_dtw_open", x, ldx, x_bstride, batch, n_rows, n_cols, max_rows, max_cols, path_text, path_time, path_ld, path_len,
+                     end_row, workspace, workspace_bytes, stream);
 }
 
 size_t wm_align_workspace_bytes(int batch, int n_heads, int cap_tokens, int n_audio_ctx) {
@@ -405,7 +502,8 @@ size_t wm_align_workspace_bytes(int batch, int n_heads, int cap_tokens, int n_au
     return carve_align(batch, n_heads, cap_tokens, n_audio_ctx).total;
 }
 
-int wm_align(const wm_align_io* io, wm_stream_t stream) {
+// wm_align (end_row == null: the closed walk) and wm_align_open
+static int align_entry(const wm_align_io* io, int32_t* end_row, wm_stream_t stream) {
     WM_REQUIRE(io && io->q_tape && io->cross && io->heads && io->n_tokens && io->n_frames && io->path_text && io->path_time &&
                io->path_len && io->workspace, "wm_align: null argument");
     const int B = io->batch, H = io->n_text_head, Tk = io->n_audio_ctx, nh = io->n_heads, cap = io->cap_tokens;
@@ -473,7 +571,14 @@ int wm_align(const wm_align_io* io, wm_stream_t stream) {
     dp.n_rows = io->n_tokens; dp.row_sub = io->n_prefix + 1; dp.n_cols = io->n_frames; dp.max_rows = cap; dp.max_cols = Tk;
     dp.path_text = io->path_text; dp.path_time = io->path_time; dp.path_ld = cap + Tk; dp.path_len = io->path_len;
     dp.trace = base + w.dtw;
-    return launch_dtw(dp, B, s);
+    return launch_dtw(dp, B, s, end_row);
+}
+
+int wm_align(const wm_align_io* io, wm_stream_t stream) { return align_entry(io, nullptr, stream); }
+
+int wm_align_open(const wm_align_io* io, int32_t* end_row, wm_stream_t stream) {
+    WM_REQUIRE(end_row, "wm_align_open: null argument");
+    return align_entry(io, end_row, stream);
 }
 
 }  // extern "C"

@@ -784,6 +784,48 @@ int wm_decoder_step_tap(const wm_engine* e, const wm_decoder_io* io, const wm_ta
     });
 }
 
+// wm_decoder_prefill with the tap behind every layer's cq projection: the block's cq sums wait in the same slabs (w.part, cq_ks) for
+// attn_prefill.hip's cross-attention kernel, and the tap adds them in that kernel's order.  Every refusal comes before the first launch.
+int wm_decoder_prefill_tap(const wm_engine* e, const wm_prefill_io* pio, const wm_tap_io* tap, wm_stream_t stream_) {
+    WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_prefill_tap: not a decoder engine");
+    WM_REQUIRE(pio && tap && tap->q_tape && tap->heads && tap->n_heads >= 1, "wm_decoder_prefill_tap: null argument");
+    const wm_decoder_io* io = &pio->io;
+    const int L = io->n_new;
+    WM_REQUIRE(!e->i8cross(), "wm_decoder_prefill_tap: engines with int8 cross K/V are not supported (the block kernels read fp16 cross K/V)");
+    WM_REQUIRE(io->batch >= 1 && L >= 1, "wm_decoder_prefill_tap: bad batch/n_new (%d, %d)", io->batch, L);
+    WM_REQUIRE(L <= e->dims.n_text_ctx, "wm_decoder_prefill_tap: n_new=%d exceeds n_text_ctx=%d", L, e->dims.n_text_ctx);
+    WM_REQUIRE(io->n_past == 0, "wm_decoder_prefill_tap: n_past=%d: the block goes on an empty cache (n_past must be 0)", io->n_past);
+    WM_REQUIRE(!io->n_past_dev, "wm_decoder_prefill_tap: a device step counter (n_past_dev) is not supported");
+    WM_REQUIRE(!io->qkv_amax, "wm_decoder_prefill_tap: the calibration hook (qkv_amax) is not supported");
+    WM_REQUIRE(!io->row_start, "wm_decoder_prefill_tap: row_start (right-aligned rows) is not supported: the forced pass runs without a prompt");
+    WM_REQUIRE(io->present, "wm_decoder_prefill_tap: present buffers are missing");
+    const int H = e->dims.n_text_head, n_layer = e->dims.n_text_layer;
+    for (int i = 0; i < n_layer; ++i) {
+        WM_REQUIRE(io->present[i], "wm_decoder_prefill_tap: present[%d] is null", i);
+        WM_REQUIRE(io->cross && io->cross[i], "wm_decoder_prefill_tap: cross[%d] is null", i);
+    }
+    WM_REQUIRE(io->present_capacity >= L, "wm_decoder_prefill_tap: present capacity %d < n_new = %d", io->present_capacity, L);
+    WM_REQUIRE(pio->logits_from >= 0 && pio->logits_from < L, "wm_decoder_prefill_tap: logits_from=%d is outside 0 .. n_new - 1 = %d", pio->logits_from, L - 1);
+    WM_REQUIRE(H <= 64, "wm_decoder_prefill_tap: %d heads per layer (at most 64)", H);
+    WM_REQUIRE(tap->capacity >= L, "wm_decoder_prefill_tap: tape capacity %d < n_new = %d", tap->capacity, L);
+    for (int k = 0; k < tap->n_heads; ++k)
+        WM_REQUIRE(tap->heads[k] >= 0 && tap->heads[k] < n_layer * H && (k == 0 || tap->heads[k] > tap->heads[k - 1]),
+                   "wm_decoder_prefill_tap: heads must be strictly ascending and below n_text_layer * n_text_head (entry %d = %d)", k, tap->heads[k]);
+    hipStream_t s = (hipStream_t)stream_;
+    GroupStep g;
+    g.prefill = true; g.logits_from = pio->logits_from;
+    if (int rc = g.init(e, io, s, false)) return rc;
+    int k = 0;
+    return g.run(s, [&](int i) {
+        int heads[64], slots[64], n = 0;
+        for (; k < tap->n_heads && tap->heads[k] / H == i; ++k) { heads[n] = tap->heads[k] % H; slots[n] = k; ++n; }
+        if (n == 0) return 0;
+        const Lin& cq = e->dec[i].cq;
+        return launch_tap_q_block(g.w.part, g.cq_ks, cq.N, (long)g.M * cq.N, cq.b, g.B, g.L, (h16*)tap->q_tape, tap->n_heads,
+                                  tap->capacity, heads, slots, n, s);
+    });
+}
+
 int wm_decoder_step_multi(const wm_engine* e, int n_groups, const wm_decoder_io* const* ios,
                           const wm_stream_t* light_streams, wm_stream_t heavy_stream) {
     WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_step_multi: not a decoder engine");

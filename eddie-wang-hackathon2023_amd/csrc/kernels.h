@@ -327,5 +327,8 @@ int launch_quantize_i8(const h16* x, int8_t* q, long n, float inv_scale, hipStre
 // index within the layer, slots: its place in the tape fp16 [B][n_tape_heads][capacity][64]), rows T .. T + L of every utterance.
 int launch_tap_q(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, int T, h16* tape,
                  int n_tape_heads, int capacity, const int* heads_in_layer, const int* slots, int n, hipStream_t stream);
+// The tap of wm_decoder_prefill_tap: rows 0 .. L of every utterance, the slabs added in attn_prefill.hip's order, any B * L.
+int launch_tap_q_block(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, h16* tape, int n_tape_heads,
+                       int capacity, const int* heads_in_layer, const int* slots, int n, hipStream_t stream);
 
 }  // namespace wm

@@ -957,7 +957,8 @@ class DeviceLoop:
         no_speech_probs = nsp_dev.tolist() if nsp_dev is not None else [np.nan] * tokens.shape[0]
         return tokens, st['sum_logprobs'].clone(), no_speech_probs
 
-    def word_timestamps(self, audio_features, results, num_frames=None, token_probs: str = "torch") -> List[List[timing.WordTiming]]:
+    def word_timestamps(self, audio_features, results, num_frames=None, token_probs: str = "torch",
+                        forced_pass: str = "steps") -> List[List[timing.WordTiming]]:
         """When each word of `results` (the DecodingResults of post_process for `audio_features`) was spoken: upstream
         Whisper's find_alignment on the device.  A second, teacher-forced pass over sot_sequence + <|notimestamps|> + text + EOT
         (4 tokens per call, wm_decoder_step_tap) records the cross-attention queries of the alignment heads; wm_align turns
@@ -970,9 +971,14 @@ class DeviceLoop:
         candidate): use torch_word_timestamps.
         `token_probs`: where the probability of every forced token is computed from the pass's logits -- "torch" (the default:
         an fp32 copy of each call's slab, logsumexp and gather) or "device" (wm_forced_probs, csrc/forced_probs.hip: the fp16
-        logits read once; long-form transcription uses it).  The two agree to fp32 rounding, not bit for bit."""
+        logits read once; long-form transcription uses it).  The two agree to fp32 rounding, not bit for bit.
+        `forced_pass`: "steps" (the default: 4 tokens per wm_decoder_step_tap call) or "block" (ONE wm_decoder_prefill_tap over the
+        whole forced sequence per row chunk, `_forced_pass_block`; forced alignment uses it).  The two tapes agree to the teacher-forced
+        bound, not bit for bit: the block's Linears run at batch x L rows and its attention kernels are attn_prefill.hip's."""
         if token_probs not in ("torch", "device"):
             raise ValueError(f"word_timestamps: token_probs = {token_probs!r}: 'torch' or 'device'")
+        if forced_pass not in ("steps", "block"):
+            raise ValueError(f"word_timestamps: forced_pass = {forced_pass!r}: 'steps' or 'block'")
         if self.n_group > 1 and not self.shared_cross_kv:
             raise ValueError("word_timestamps: beam_size / best_of > 1 is not supported on the device path in this version "
                              "unless the instance shares its cross K/V (shared_cross_kv=True; torch_word_timestamps has no such limit)")
@@ -995,7 +1001,10 @@ class DeviceLoop:
             raise ValueError(f"word_timestamps: a forced sequence of {L} tokens exceeds n_text_ctx = {cap}")
         heads = self.alignment_heads()
         heads_arr = (C.c_int32 * len(heads))(*heads)
-        tape, probs, cross = self._forced_pass(audio_features, forced, L, heads_arr, token_probs)
+        if forced_pass == "block":
+            tape, probs, cross = self._forced_pass_block(audio_features, forced, L, heads_arr, token_probs)
+        else:
+            tape, probs, cross = self._forced_pass(audio_features, forced, L, heads_arr, token_probs)
         pt, pf, lens, matrix = self._align(cross, tape, heads_arr, n_all, frames, L)
         probs = probs.cpu()
         self.last_alignment = dict(path_text=pt, path_time=pf, path_len=lens, n_tokens=n_all, n_frames=frames,
@@ -1034,6 +1043,53 @@ class DeviceLoop:
                 lf = lg[:, :, :eot].float()
                 nxt = rows[lo:hi, off + 1: off + l + 1].long().clamp(max=eot - 1)
                 probs[lo:hi, off:off + l] = (lf.gather(-1, nxt[..., None])[..., 0] - lf.logsumexp(dim=-1)).exp()
+        return tape, probs, cross
+
+    BLOCK_LOGIT_BYTES = 1 << 30        # the fp16 logits [rows, L, V] of one wm_decoder_prefill_tap call: the rows are chunked to fit
+
+    def block_pass_rows(self, L: int) -> int:
+        """Rows of one block call: what keeps its [rows, L, V] fp16 logits within BLOCK_LOGIT_BYTES (77 rows at 133 tokens of a
+        51 865-token vocabulary), at least one."""
+        return max(1, self.BLOCK_LOGIT_BYTES // (max(1, L) * self.decoder_config['vocab_size'] * 2))
+
+    def _forced_pass_block(self, audio_features, forced, L, heads_arr, token_probs: str, buffers: Optional[dict] = None):
+        """`_forced_pass` as ONE block per row chunk (wm_decoder_prefill_tap, logits from position 0 on): the same three values.
+        `buffers`: a dict the caller keeps between calls -- the tape [n, n_heads, capacity >= L, 64], `probs` fp32 [n, capacity] and
+        the logits slab live there and are reused (forced alignment: fixed for the call); without it they are allocated here, the
+        tape and the probabilities at [.., L]."""
+        dev, cfg, eot = audio_features.device, self.decoder_config, self.tokenizer.eot
+        n, V, cap = audio_features.shape[0], cfg['vocab_size'], cfg['num_text_ctx']
+        rows = torch.full((n, L + 1), eot, dtype=torch.int32)
+        for b, (_, f) in enumerate(forced):
+            rows[b, :len(f)] = torch.tensor(f, dtype=torch.int32)
+        rows = rows.to(dev)
+        lib, sess, pos = native.load_library(), self.decoder_session, self.positional_embedding
+        st = self._fast_state(n * self._cross_group(), dev)
+        cross = self._cross_persistent(audio_features, st)
+        stream = torch.cuda.current_stream().cuda_stream
+        chunk = min(n, self.block_pass_rows(L))
+        if buffers is None:
+            buffers = {}
+        if 'tape' not in buffers:
+            buffers['tape'] = torch.empty((n, len(heads_arr), L, 64), dtype=torch.float16, device=dev)
+            buffers['probs'] = torch.zeros((n, L), dtype=torch.float32, device=dev)
+        if buffers.get('logits') is None or buffers['logits'].numel() < chunk * L * V:
+            buffers['logits'] = torch.empty(chunk * L * V, dtype=torch.float16, device=dev)
+        tape, probs, logits = buffers['tape'], buffers['probs'], buffers['logits']
+        assert tape.shape[0] == n and tape.shape[2] >= L and probs.shape[0] == n and probs.stride(0) >= L
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            kv, cr = [t[lo:hi] for t in st['kv']], [t[lo:hi] for t in cross]
+            lg = logits[: (hi - lo) * L * V].view(hi - lo, L, V)
+            sess.decoder_prefill_tap(rows[lo:hi, :L], pos[0:L], cr, kv, cap, lg, stream, 0, tape[lo:hi], heads_arr, slot=2000)
+            if token_probs == "device":
+                native.check(lib.wm_forced_probs(lg.data_ptr(), hi - lo, L, V, L * V, V, eot, rows[lo:hi, 1:].data_ptr(), L + 1,
+                                                 probs[lo:hi].data_ptr(), probs.stride(0), stream), "wm_forced_probs")
+                continue
+            for b in range(hi - lo):               # (one row's [L, eot] fp32 slab at a time)
+                lf = lg[b, :, :eot].float()
+                nxt = rows[lo + b, 1: L + 1].long().clamp(max=eot - 1)
+                probs[lo + b, :L] = (lf.gather(-1, nxt[:, None])[:, 0] - lf.logsumexp(dim=-1)).exp()
         return tape, probs, cross
 
     def _align(self, cross, tape, heads_arr, n_all, frames, L):

@@ -94,6 +94,7 @@ EXPORTS = (
     "wm_sequence_bias",
     "wm_sample_step",
     "wm_resample_channels", "wm_channel_top_workspace_bytes", "wm_channel_top",
+    "wm_dtw_open", "wm_align_open", "wm_decoder_prefill_tap",
 )
 
 
@@ -487,6 +488,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_dtw_workspace_bytes.argtypes = [i32, i32, i32]
     lib.wm_dtw_workspace_bytes.restype = sz
     lib.wm_dtw.argtypes = [vp, i32, C.c_int64, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]
+    lib.wm_dtw_open.argtypes = [vp, i32, C.c_int64, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.wm_align_open.argtypes = [C.POINTER(WmAlignIO), vp, vp]
+    lib.wm_decoder_prefill_tap.argtypes = [vp, C.POINTER(WmPrefillIO), C.POINTER(WmTapIO), vp]
     lib.wm_profile_configure.argtypes = [i32, i32, i32]
     lib.wm_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
     _lib = lib

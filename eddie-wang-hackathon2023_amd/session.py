@@ -316,6 +316,20 @@ class Session(object):
         tap.heads, tap.n_heads = C.cast(heads, C.POINTER(C.c_int32)), len(heads)
         check(self._engine.lib.wm_decoder_step_tap(self._engine.handle, C.byref(io), C.byref(tap), stream), "wm_decoder_step_tap")
 
+    def decoder_prefill_tap(self, tokens, pos, cross, present, capacity, logits, stream: int, logits_from: int, q_tape: torch.Tensor,
+                            heads, slot: int = 0):
+        """wm_decoder_prefill_tap: `decoder_prefill` with the cross-attention queries of `heads` (as decoder_step_tap) written to rows
+        0 .. L - 1 of q_tape fp16 [B, len(heads), capacity, 64]."""
+        pio = native.WmPrefillIO()
+        pio.io = self.make_decoder_io(tokens, pos, cross, None, 0, present, capacity, logits, 0, slot=slot, prefill=True)
+        pio.logits_from = int(logits_from)
+        pio._keep = pio.io
+        assert q_tape.dtype == torch.float16 and q_tape.is_contiguous() and q_tape.shape[0] == tokens.shape[0] and q_tape.shape[1] == len(heads)
+        tap = native.WmTapIO()
+        tap.q_tape, tap.capacity = q_tape.data_ptr(), q_tape.shape[2]
+        tap.heads, tap.n_heads = C.cast(heads, C.POINTER(C.c_int32)), len(heads)
+        check(self._engine.lib.wm_decoder_prefill_tap(self._engine.handle, C.byref(pio), C.byref(tap), stream), "wm_decoder_prefill_tap")
+
     def decoder_step_multi(self, ios: Sequence[WmDecoderIO], light_streams: Sequence[int], heavy_stream: int):
         """One decode step of several utterance groups, interleaved layer by layer (wm_decoder_step_multi):
         each group's short kernels on its own light stream, all cross-attention kernels on `heavy_stream`."""

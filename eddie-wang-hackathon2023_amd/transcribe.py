@@ -491,6 +491,12 @@ def transcribe(encoding: WhisperEncoding, decoding: WhisperDecoding, audio_or_pa
     return transcribe_mel(encoding, decoding, mels, content, **kw)
 
 
+# Forced alignment -- the text is given, the times are asked for -- shares the schedule, not the code: forced_align.py (alignment.py
+# states its contract).  `sections`, `speech` and `channels` do not combine with it.
+from alignment import AlignOptions  # noqa: E402,F401 (re-exported)
+from forced_align import align, align_mel  # noqa: E402,F401 (re-exported)
+
+
 def format_timestamp(seconds: float) -> str:
     ms = round(seconds * 1000.0)
     return f"{ms // 60000:02d}:{ms % 60000 // 1000:02d}.{ms % 1000:03d}"

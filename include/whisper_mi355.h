@@ -74,7 +74,8 @@ typedef struct wm_dims {
  *      (still 8: a test-only entry and a struct of its own) wm_attn_encoder_ex / wm_attn_encoder_io
  *      (still 8: an entry and structs of its own) wm_sequence_bias / wm_bias_io / wm_bias_item
  *      (still 8: an entry and a struct of its own) wm_sample_step / wm_sample_io
- *      (still 8: entries only) wm_resample_channels, wm_channel_top, wm_channel_top_workspace_bytes */
+ *      (still 8: entries only) wm_resample_channels, wm_channel_top, wm_channel_top_workspace_bytes
+ *      (still 8: entries only) wm_dtw_open, wm_align_open, wm_decoder_prefill_tap */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -509,6 +510,31 @@ size_t wm_dtw_workspace_bytes(int batch, int max_rows, int max_cols);
 int wm_dtw(const float* x, int ldx, int64_t x_bstride, int batch, const int32_t* n_rows, const int32_t* n_cols, int max_rows,
            int max_cols, int32_t* path_text, int32_t* path_time, int path_ld, int32_t* path_len, void* workspace,
            size_t workspace_bytes, wm_stream_t stream);
+
+/* ---- forced alignment (added within ABI 8: new entries only, no existing struct or signature changed) ----------------------
+ * Placing a transcript the caller already has: a window of a long file holds an unknown prefix of the remaining text, so the
+ * walk's end is free on the token axis, and the forced pass is one block (alignment.py is the host form).
+ *
+ * wm_dtw_open = wm_dtw with an open end: the cost table and the trace codes are wm_dtw's, cell for cell; the walk back starts at
+ * (i*, n_cols), i* = the smallest i in 1 .. n_rows with cost[i][n_cols] <= cost[k][n_cols] for every k in 1 .. n_rows (fp32
+ * compares; the costs are not normalised by the path's length).  end_row (device int32 [batch]) receives i*, 0 (with path_len 0)
+ * where n_rows[b] < 1 or n_cols[b] < 1.  One launch; thread i keeps cost[i][n_cols] when it computes it and the arg-min is one
+ * shuffle reduction per wave plus one pass over the waves' results in LDS.  Shape limits, workspace (wm_dtw_workspace_bytes)
+ * and everything else written: wm_dtw's.                                                                                   */
+int wm_dtw_open(const float* x, int ldx, int64_t x_bstride, int batch, const int32_t* n_rows, const int32_t* n_cols, int max_rows,
+                int max_cols, int32_t* path_text, int32_t* path_time, int path_ld, int32_t* path_len, int32_t* end_row,
+                void* workspace, size_t workspace_bytes, wm_stream_t stream);
+/* wm_align with wm_dtw_open's walk in place of the closed one: the matrix (the z-score runs over all n_tokens[b] rows) and the
+ * median filter are wm_align's bit for bit; end_row[b] counts rows of `matrix` (1 .. N), 0 where the utterance has no path.   */
+int wm_align_open(const wm_align_io* io, int32_t* end_row, wm_stream_t stream);
+/* wm_decoder_prefill with wm_decoder_step_tap's hook: behind the cross-attention query projection of every layer that has a
+ * listed head, one small kernel adds the block's split-K slabs and the bias in the block cross-attention kernel's own order
+ * (rounds of four slabs, then the rest one by one) and writes r16(q_sum + bias) of the listed heads to rows 0 .. n_new - 1 of
+ * q_tape; rows beyond are not touched.  Its grid folds the row index, so batch * n_new may pass 65 535.  Logits (from
+ * logits_from on) and the appended cache are wm_decoder_prefill's bit for bit.  Refused (rc 1) before the first launch: whatever
+ * wm_decoder_prefill refuses, io.row_start, and the head lists wm_decoder_step_tap refuses; tap->capacity >= n_new.
+ * Workspace: wm_decoder_prefill_workspace_bytes.                                                                            */
+int wm_decoder_prefill_tap(const wm_engine* e, const wm_prefill_io* io, const wm_tap_io* tap, wm_stream_t stream);
 
 /* ---- kernel-level entry points (parity tests, micro-benchmarks, roofline measurement) -----------*/
 /* C[M,N] = act(A[M,K] x W[N,K]^T * scale + bias) (+ residual); W fp16 or int8 (w8) row-major [N][K].
