@@ -14,7 +14,7 @@
 //   dtw_kernel        one workgroup per utterance walks the anti-diagonals (the last three in LDS, one barrier each, trace bytes in
 //                     the workspace), then walks back and writes the reversed path.
 // Forced alignment (its host form alignment.py) adds the open end of that walk (wm_dtw_open, wm_align_open: the same
-// kernel, templated) and the tap of a whole block (tap_q_block_kernel behind wm_decoder_prefill_tap).
+// kernel, templated).  The tap is ONE kernel behind a 4-token step (wm_decoder_step_tap) and a whole block (wm_decoder_prefill_tap).
 #include "decode_math.h"
 #include "kernels.h"
 #include "../../include/whisper_mi355.h"
@@ -41,34 +41,20 @@ __device__ __forceinline__ half8v scale8(half8v x) {
 // ---- the tap ------------------------------------------------------------------------------------------------------------------------
 struct TapLayer { int n; unsigned char head[64]; short slot[64]; };
 
-// q = r16(sum of the split-K slabs + bias) of the listed heads of one layer, added as the cross-attention kernel adds them
-// (attn_decode.hip: qa += slab s + slab s+1, absent slabs add 0)
-__global__ __launch_bounds__(64) void tap_q_kernel(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int L, int T,
-                                                   h16* tape, int n_tape_heads, int capacity, TapLayer tl) {
-    const int d = threadIdx.x, hi = blockIdx.x, row = blockIdx.y;
-    const int b = row / L, l = row - b * L;
-    const int col = (int)tl.head[hi] * 64 + d;
-    const float* src = part + (size_t)row * ldp + col;
+// The tape has to hold the q its cross-attention kernel saw, so the split-K slabs are added in that kernel's order.  The two orders
+// agree up to 5 slabs (the shipped cap is 4) and round differently from 6 on (WM_KSPLIT_CAP): they are not to be merged.
+// TAP_PAIRS must match attn_cross_kernel in attn_decode.hip: qa += slab s + slab s+1, absent slabs add 0
+__device__ __forceinline__ float slab_sum_pairs(const float* src, int ksplit, long sstride) {
     float qa = 0.f;
     for (int s = 0; s < ksplit; s += 2) {
         const float x0 = src[(size_t)s * sstride];
         const float x1 = s + 1 < ksplit ? src[(size_t)(s + 1) * sstride] : 0.f;
         qa += x0 + x1;
     }
-    const float bs = bias ? (float)bias[col] : 0.f;
-    tape[(((size_t)b * n_tape_heads + tl.slot[hi]) * capacity + T + l) * 64 + d] = (h16)(qa + bs);
+    return qa;
 }
-
-// The same for a whole block (wm_decoder_prefill_tap): the slabs added in attn_prefill.hip's order (slab_row8: rounds of four, then a
-// tail one by one), the row index folded over blockIdx.y and .z (a block of 224 tokens x 576 rows passes 65 535)
-__global__ __launch_bounds__(64) void tap_q_block_kernel(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int L, int n_rows,
-                                                         h16* tape, int n_tape_heads, int capacity, TapLayer tl) {
-    const int d = threadIdx.x, hi = blockIdx.x;
-    const long row = (long)blockIdx.z * gridDim.y + blockIdx.y;
-    if (row >= n_rows) return;
-    const int b = (int)(row / L), l = (int)(row - (long)b * L);
-    const int col = (int)tl.head[hi] * 64 + d;
-    const float* src = part + (size_t)row * ldp + col;
+// TAP_FOURS must match slab_row8 in attn_prefill.hip: rounds of four, then a tail one by one
+__device__ __forceinline__ float slab_sum_fours(const float* src, int ksplit, long sstride) {
     float qa = 0.f;
     int s = 0;
     for (; s + 4 <= ksplit; s += 4) {
@@ -77,8 +63,23 @@ __global__ __launch_bounds__(64) void tap_q_block_kernel(const float* part, int 
         qa += (x0 + x1) + (x2 + x3);
     }
     for (; s < ksplit; ++s) qa += src[(size_t)s * sstride];
+    return qa;
+}
+
+// q = r16(sum of the split-K slabs + bias) of the listed heads of one layer, for the n_rows = B * L rows of a call, to the tape rows
+// T .. T + L - 1 of every utterance.  The row index is folded over blockIdx.y and .z (a block of 224 tokens x 576 rows passes 65 535).
+template <TapOrder ORDER>
+__global__ __launch_bounds__(64) void tap_q_kernel(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int L, int T, int n_rows,
+                                                   h16* tape, int n_tape_heads, int capacity, TapLayer tl) {
+    const int d = threadIdx.x, hi = blockIdx.x;
+    const unsigned folded = blockIdx.z * gridDim.y + blockIdx.y;           // (< 2^32: at most 32 769 planes of 65 535)
+    if (folded >= (unsigned)n_rows) return;
+    const int row = (int)folded, b = row / L, l = row - b * L;
+    const int col = (int)tl.head[hi] * 64 + d;
+    const float* src = part + (size_t)row * ldp + col;
+    const float qa = ORDER == TAP_PAIRS ? slab_sum_pairs(src, ksplit, sstride) : slab_sum_fours(src, ksplit, sstride);
     const float bs = bias ? (float)bias[col] : 0.f;
-    tape[(((size_t)b * n_tape_heads + tl.slot[hi]) * capacity + l) * 64 + d] = (h16)(qa + bs);
+    tape[(((size_t)b * n_tape_heads + tl.slot[hi]) * capacity + T + l) * 64 + d] = (h16)(qa + bs);
 }
 
 // ---- the alignment matrix -----------------------------------------------------------------------------------------------------------
@@ -429,28 +430,18 @@ AlignWs carve_align(int batch, int n_heads, int cap_tokens, int Tk) {
 
 }  // namespace
 
-int launch_tap_q(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, int T, h16* tape,
+int launch_tap_q(TapOrder order, const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, int T, h16* tape,
                  int n_tape_heads, int capacity, const int* heads_in_layer, const int* slots, int n, hipStream_t s) {
     WM_REQUIRE(n >= 1 && n <= 64, "tap: %d heads in one layer", n);
+    WM_REQUIRE(B >= 1 && L >= 1 && T >= 0 && T + L <= capacity && (long)B * L <= 0x7fffffffL,
+               "tap: bad block (%d rows x %d tokens behind %d, capacity %d)", B, L, T, capacity);
     TapLayer tl{};
     tl.n = n;
     for (int k = 0; k < n; ++k) { tl.head[k] = (unsigned char)heads_in_layer[k]; tl.slot[k] = (short)slots[k]; }
-    hipLaunchKernelGGL(tap_q_kernel, dim3(n, B * L), dim3(64), 0, s, part, ksplit, ldp, sstride, bias, L, T, tape, n_tape_heads, capacity, tl);
+    const int n_rows = B * L, gy = n_rows < 65535 ? n_rows : 65535, gz = (n_rows + gy - 1) / gy;      // (gz <= 32 769: n_rows is an int)
+    const auto kernel = order == TAP_PAIRS ? tap_q_kernel<TAP_PAIRS> : tap_q_kernel<TAP_FOURS>;
+    hipLaunchKernelGGL(kernel, dim3(n, gy, gz), dim3(64), 0, s, part, ksplit, ldp, sstride, bias, L, T, n_rows, tape, n_tape_heads, capacity, tl);
     WM_LAUNCH_CHECK(s, "tap_q");
-    return 0;
-}
-
-int launch_tap_q_block(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, h16* tape, int n_tape_heads,
-                       int capacity, const int* heads_in_layer, const int* slots, int n, hipStream_t s) {
-    WM_REQUIRE(n >= 1 && n <= 64, "tap: %d heads in one layer", n);
-    WM_REQUIRE(B >= 1 && L >= 1 && L <= capacity && (long)B * L <= 0x7fffffffL, "tap: bad block (%d rows x %d tokens, capacity %d)", B, L, capacity);
-    TapLayer tl{};
-    tl.n = n;
-    for (int k = 0; k < n; ++k) { tl.head[k] = (unsigned char)heads_in_layer[k]; tl.slot[k] = (short)slots[k]; }
-    const int n_rows = B * L, gy = n_rows < 65535 ? n_rows : 65535, gz = (n_rows + gy - 1) / gy;
-    WM_REQUIRE(gz <= 65535, "tap: %d rows", n_rows);
-    hipLaunchKernelGGL(tap_q_block_kernel, dim3(n, gy, gz), dim3(64), 0, s, part, ksplit, ldp, sstride, bias, L, n_rows, tape, n_tape_heads, capacity, tl);
-    WM_LAUNCH_CHECK(s, "tap_q_block");
     return 0;
 }
 

@@ -725,28 +725,34 @@ size_t wm_decoder_prefill_workspace_bytes(const wm_engine* e, int batch, int n_n
     return carve_decoder(e, batch, n_new, nullptr, 1, true).total;
 }
 
-int wm_decoder_prefill(const wm_engine* e, const wm_prefill_io* pio, wm_stream_t stream_) {
-    WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_prefill: not a decoder engine");
-    WM_REQUIRE(pio, "wm_decoder_prefill: null argument");
+// what wm_decoder_prefill and wm_decoder_prefill_tap refuse about the block itself; `who` is the entry a refusal names
+static int check_block_call(const char* who, const wm_engine* e, const wm_prefill_io* pio) {
+    WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "%s: not a decoder engine", who);
+    WM_REQUIRE(pio, "%s: null argument", who);
     const wm_decoder_io* io = &pio->io;
     const int L = io->n_new;
-    WM_REQUIRE(!e->i8cross(), "wm_decoder_prefill: engines with int8 cross K/V are not supported (the block kernels read fp16 cross K/V)");
-    WM_REQUIRE(io->batch >= 1 && L >= 1, "wm_decoder_prefill: bad batch/n_new (%d, %d)", io->batch, L);
-    WM_REQUIRE(L <= e->dims.n_text_ctx, "wm_decoder_prefill: n_new=%d exceeds n_text_ctx=%d", L, e->dims.n_text_ctx);
-    WM_REQUIRE(io->n_past == 0, "wm_decoder_prefill: n_past=%d: the block goes on an empty cache (n_past must be 0)", io->n_past);
-    WM_REQUIRE(!io->n_past_dev, "wm_decoder_prefill: a device step counter (n_past_dev) is not supported");
-    WM_REQUIRE(!io->qkv_amax, "wm_decoder_prefill: the calibration hook (qkv_amax) is not supported");
-    WM_REQUIRE(io->present, "wm_decoder_prefill: present buffers are missing");
+    WM_REQUIRE(!e->i8cross(), "%s: engines with int8 cross K/V are not supported (the block kernels read fp16 cross K/V)", who);
+    WM_REQUIRE(io->batch >= 1 && L >= 1, "%s: bad batch/n_new (%d, %d)", who, io->batch, L);
+    WM_REQUIRE(L <= e->dims.n_text_ctx, "%s: n_new=%d exceeds n_text_ctx=%d", who, L, e->dims.n_text_ctx);
+    WM_REQUIRE(io->n_past == 0, "%s: n_past=%d: the block goes on an empty cache (n_past must be 0)", who, io->n_past);
+    WM_REQUIRE(!io->n_past_dev, "%s: a device step counter (n_past_dev) is not supported", who);
+    WM_REQUIRE(!io->qkv_amax, "%s: the calibration hook (qkv_amax) is not supported", who);
+    WM_REQUIRE(io->present, "%s: present buffers are missing", who);
     for (int i = 0; i < e->dims.n_text_layer; ++i) {
-        WM_REQUIRE(io->present[i], "wm_decoder_prefill: present[%d] is null", i);
-        WM_REQUIRE(io->cross && io->cross[i], "wm_decoder_prefill: cross[%d] is null", i);
+        WM_REQUIRE(io->present[i], "%s: present[%d] is null", who, i);
+        WM_REQUIRE(io->cross && io->cross[i], "%s: cross[%d] is null", who, i);
     }
-    WM_REQUIRE(io->present_capacity >= L, "wm_decoder_prefill: present capacity %d < n_new = %d", io->present_capacity, L);
-    WM_REQUIRE(pio->logits_from >= 0 && pio->logits_from < L, "wm_decoder_prefill: logits_from=%d is outside 0 .. n_new - 1 = %d", pio->logits_from, L - 1);
+    WM_REQUIRE(io->present_capacity >= L, "%s: present capacity %d < n_new = %d", who, io->present_capacity, L);
+    WM_REQUIRE(pio->logits_from >= 0 && pio->logits_from < L, "%s: logits_from=%d is outside 0 .. n_new - 1 = %d", who, pio->logits_from, L - 1);
+    return 0;
+}
+
+int wm_decoder_prefill(const wm_engine* e, const wm_prefill_io* pio, wm_stream_t stream_) {
+    if (int rc = check_block_call("wm_decoder_prefill", e, pio)) return rc;
     hipStream_t s = (hipStream_t)stream_;
     GroupStep g;
     g.prefill = true; g.logits_from = pio->logits_from;
-    if (int rc = g.init(e, io, s, false)) return rc;
+    if (int rc = g.init(e, &pio->io, s, false)) return rc;
     return g.run(s);
 }
 
@@ -755,75 +761,62 @@ int wm_decoder_step_group(const wm_engine* e, const wm_decoder_group_io* gio, wm
     return decoder_step(e, &gio->io, gio->cross_group, gio->live_groups, stream);
 }
 
-// wm_decoder_step on the launch-per-kernel path, with the cross-attention queries of the listed heads written to the tape: behind
-// the cq projection of a layer the sums wait in the workspace for the cross-attention kernel (split-K slabs, or one slab from the
-// fused forms), where the tap kernel reads them too, in that kernel's order (align.hip).
-int wm_decoder_step_tap(const wm_engine* e, const wm_decoder_io* io, const wm_tap_io* tap, wm_stream_t stream_) {
-    WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_step_tap: not a decoder engine");
-    WM_REQUIRE(io && tap && tap->q_tape && tap->heads && tap->n_heads >= 1, "wm_decoder_step_tap: null argument");
-    WM_REQUIRE(io->n_new >= 1 && io->n_new <= DEC_CHUNK && !io->n_past_dev, "wm_decoder_step_tap: n_new must be 1 .. %d, without a device step counter", DEC_CHUNK);
-    WM_REQUIRE(!io->row_start, "wm_decoder_step_tap: row_start (right-aligned rows) is not supported: word timestamps are computed without a prompt");
-    const int H = e->dims.n_text_head, n_layer = e->dims.n_text_layer;
-    WM_REQUIRE(H <= 64, "wm_decoder_step_tap: %d heads per layer (at most 64)", H);
-    WM_REQUIRE(io->n_past >= 0 && tap->capacity >= io->n_past + io->n_new, "wm_decoder_step_tap: tape capacity %d < n_past + n_new = %d", tap->capacity,
-               io->n_past + io->n_new);
+// The tapped entries: wm_decoder_step / wm_decoder_prefill on the launch-per-kernel path, with the cross-attention queries of the
+// listed heads written to the tape.  Behind the cq projection of a layer the sums wait in the workspace (w.part, cq_ks split-K slabs,
+// or one slab from the fused forms) for the cross-attention kernel, where the tap kernel reads them too, in that kernel's order
+// (align.hip).  Every refusal comes before the first launch.
+
+// what both refuse about a wm_tap_io (e: a decoder engine); `who` is the entry a refusal names
+static int check_tap(const char* who, const wm_engine* e, const wm_tap_io* tap) {
+    WM_REQUIRE(tap && tap->q_tape && tap->heads && tap->n_heads >= 1, "%s: null argument", who);
+    const int H = e->dims.n_text_head;
+    WM_REQUIRE(H <= 64, "%s: %d heads per layer (at most 64)", who, H);
     for (int k = 0; k < tap->n_heads; ++k)
-        WM_REQUIRE(tap->heads[k] >= 0 && tap->heads[k] < n_layer * H && (k == 0 || tap->heads[k] > tap->heads[k - 1]),
-                   "wm_decoder_step_tap: heads must be strictly ascending and below n_text_layer * n_text_head (entry %d = %d)", k, tap->heads[k]);
-    hipStream_t s = (hipStream_t)stream_;
-    GroupStep g;
-    if (int rc = g.init(e, io, s, false)) return rc;
+        WM_REQUIRE(tap->heads[k] >= 0 && tap->heads[k] < e->dims.n_text_layer * H && (k == 0 || tap->heads[k] > tap->heads[k - 1]),
+                   "%s: heads must be strictly ascending and below n_text_layer * n_text_head (entry %d = %d)", who, k, tap->heads[k]);
+    return 0;
+}
+
+// the walk over the layers with, behind pre_cross(i), the tap of the heads of layer i (tap->heads is ascending: layer by layer)
+static int run_tapped(GroupStep& g, const wm_tap_io* tap, hipStream_t s) {
+    const int H = g.H;
     int k = 0;
     return g.run(s, [&](int i) {
         int heads[64], slots[64], n = 0;
         for (; k < tap->n_heads && tap->heads[k] / H == i; ++k) { heads[n] = tap->heads[k] % H; slots[n] = k; ++n; }
         if (n == 0) return 0;
-        const Lin& cq = e->dec[i].cq;
-        return launch_tap_q(g.w.part, g.cq_ks, cq.N, (long)g.M * cq.N, cq.b, g.B, g.L, g.T, (h16*)tap->q_tape, tap->n_heads,
-                            tap->capacity, heads, slots, n, s);
+        const Lin& cq = g.e->dec[i].cq;
+        return launch_tap_q(g.prefill ? TAP_FOURS : TAP_PAIRS, g.w.part, g.cq_ks, cq.N, (long)g.M * cq.N, cq.b, g.B, g.L, g.T,
+                            (h16*)tap->q_tape, tap->n_heads, tap->capacity, heads, slots, n, s);
     });
 }
 
-// wm_decoder_prefill with the tap behind every layer's cq projection: the block's cq sums wait in the same slabs (w.part, cq_ks) for
-// attn_prefill.hip's cross-attention kernel, and the tap adds them in that kernel's order.  Every refusal comes before the first launch.
+int wm_decoder_step_tap(const wm_engine* e, const wm_decoder_io* io, const wm_tap_io* tap, wm_stream_t stream_) {
+    const char* who = "wm_decoder_step_tap";
+    WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "%s: not a decoder engine", who);
+    WM_REQUIRE(io, "%s: null argument", who);
+    if (int rc = check_tap(who, e, tap)) return rc;
+    WM_REQUIRE(io->n_new >= 1 && io->n_new <= DEC_CHUNK && !io->n_past_dev, "%s: n_new must be 1 .. %d, without a device step counter", who, DEC_CHUNK);
+    WM_REQUIRE(!io->row_start, "%s: row_start (right-aligned rows) is not supported: word timestamps are computed without a prompt", who);
+    WM_REQUIRE(io->n_past >= 0 && tap->capacity >= io->n_past + io->n_new, "%s: tape capacity %d < n_past + n_new = %d", who, tap->capacity,
+               io->n_past + io->n_new);
+    hipStream_t s = (hipStream_t)stream_;
+    GroupStep g;
+    if (int rc = g.init(e, io, s, false)) return rc;
+    return run_tapped(g, tap, s);
+}
+
 int wm_decoder_prefill_tap(const wm_engine* e, const wm_prefill_io* pio, const wm_tap_io* tap, wm_stream_t stream_) {
-    WM_REQUIRE(e && e->kind == WM_ENGINE_DECODER, "wm_decoder_prefill_tap: not a decoder engine");
-    WM_REQUIRE(pio && tap && tap->q_tape && tap->heads && tap->n_heads >= 1, "wm_decoder_prefill_tap: null argument");
-    const wm_decoder_io* io = &pio->io;
-    const int L = io->n_new;
-    WM_REQUIRE(!e->i8cross(), "wm_decoder_prefill_tap: engines with int8 cross K/V are not supported (the block kernels read fp16 cross K/V)");
-    WM_REQUIRE(io->batch >= 1 && L >= 1, "wm_decoder_prefill_tap: bad batch/n_new (%d, %d)", io->batch, L);
-    WM_REQUIRE(L <= e->dims.n_text_ctx, "wm_decoder_prefill_tap: n_new=%d exceeds n_text_ctx=%d", L, e->dims.n_text_ctx);
-    WM_REQUIRE(io->n_past == 0, "wm_decoder_prefill_tap: n_past=%d: the block goes on an empty cache (n_past must be 0)", io->n_past);
-    WM_REQUIRE(!io->n_past_dev, "wm_decoder_prefill_tap: a device step counter (n_past_dev) is not supported");
-    WM_REQUIRE(!io->qkv_amax, "wm_decoder_prefill_tap: the calibration hook (qkv_amax) is not supported");
-    WM_REQUIRE(!io->row_start, "wm_decoder_prefill_tap: row_start (right-aligned rows) is not supported: the forced pass runs without a prompt");
-    WM_REQUIRE(io->present, "wm_decoder_prefill_tap: present buffers are missing");
-    const int H = e->dims.n_text_head, n_layer = e->dims.n_text_layer;
-    for (int i = 0; i < n_layer; ++i) {
-        WM_REQUIRE(io->present[i], "wm_decoder_prefill_tap: present[%d] is null", i);
-        WM_REQUIRE(io->cross && io->cross[i], "wm_decoder_prefill_tap: cross[%d] is null", i);
-    }
-    WM_REQUIRE(io->present_capacity >= L, "wm_decoder_prefill_tap: present capacity %d < n_new = %d", io->present_capacity, L);
-    WM_REQUIRE(pio->logits_from >= 0 && pio->logits_from < L, "wm_decoder_prefill_tap: logits_from=%d is outside 0 .. n_new - 1 = %d", pio->logits_from, L - 1);
-    WM_REQUIRE(H <= 64, "wm_decoder_prefill_tap: %d heads per layer (at most 64)", H);
-    WM_REQUIRE(tap->capacity >= L, "wm_decoder_prefill_tap: tape capacity %d < n_new = %d", tap->capacity, L);
-    for (int k = 0; k < tap->n_heads; ++k)
-        WM_REQUIRE(tap->heads[k] >= 0 && tap->heads[k] < n_layer * H && (k == 0 || tap->heads[k] > tap->heads[k - 1]),
-                   "wm_decoder_prefill_tap: heads must be strictly ascending and below n_text_layer * n_text_head (entry %d = %d)", k, tap->heads[k]);
+    const char* who = "wm_decoder_prefill_tap";
+    if (int rc = check_block_call(who, e, pio)) return rc;
+    WM_REQUIRE(!pio->io.row_start, "%s: row_start (right-aligned rows) is not supported: the forced pass runs without a prompt", who);
+    if (int rc = check_tap(who, e, tap)) return rc;
+    WM_REQUIRE(tap->capacity >= pio->io.n_new, "%s: tape capacity %d < n_new = %d", who, tap->capacity, pio->io.n_new);
     hipStream_t s = (hipStream_t)stream_;
     GroupStep g;
     g.prefill = true; g.logits_from = pio->logits_from;
-    if (int rc = g.init(e, io, s, false)) return rc;
-    int k = 0;
-    return g.run(s, [&](int i) {
-        int heads[64], slots[64], n = 0;
-        for (; k < tap->n_heads && tap->heads[k] / H == i; ++k) { heads[n] = tap->heads[k] % H; slots[n] = k; ++n; }
-        if (n == 0) return 0;
-        const Lin& cq = e->dec[i].cq;
-        return launch_tap_q_block(g.w.part, g.cq_ks, cq.N, (long)g.M * cq.N, cq.b, g.B, g.L, (h16*)tap->q_tape, tap->n_heads,
-                                  tap->capacity, heads, slots, n, s);
-    });
+    if (int rc = g.init(e, &pio->io, s, false)) return rc;
+    return run_tapped(g, tap, s);
 }
 
 int wm_decoder_step_multi(const wm_engine* e, int n_groups, const wm_decoder_io* const* ios,

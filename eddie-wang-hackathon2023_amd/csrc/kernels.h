@@ -323,12 +323,12 @@ int launch_log_mel(const float* audio, int batch, int n_samples, long audio_ld, 
 int launch_quantize_i8(const h16* x, int8_t* q, long n, float inv_scale, hipStream_t stream);
 
 // ---------------------------------------------------------------- align.hip
-// The cross-attention query tap of wm_decoder_step_tap: r16(split-K slabs + bias) of `n` heads of one layer (heads_in_layer: head
-// index within the layer, slots: its place in the tape fp16 [B][n_tape_heads][capacity][64]), rows T .. T + L of every utterance.
-int launch_tap_q(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, int T, h16* tape,
+// The cross-attention query tap: r16(split-K slabs + bias) of `n` heads of one layer (heads_in_layer: head index within the layer,
+// slots: its place in the tape fp16 [B][n_tape_heads][capacity][64]), rows T .. T + L of every utterance, any B * L.  The slabs are
+// added in the order of the cross-attention kernel that reads them next: TAP_PAIRS behind a step (attn_decode.hip), TAP_FOURS behind
+// a block (attn_prefill.hip).
+enum TapOrder { TAP_PAIRS, TAP_FOURS };
+int launch_tap_q(TapOrder order, const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, int T, h16* tape,
                  int n_tape_heads, int capacity, const int* heads_in_layer, const int* slots, int n, hipStream_t stream);
-// The tap of wm_decoder_prefill_tap: rows 0 .. L of every utterance, the slabs added in attn_prefill.hip's order, any B * L.
-int launch_tap_q_block(const float* part, int ksplit, int ldp, long sstride, const h16* bias, int B, int L, h16* tape, int n_tape_heads,
-                       int capacity, const int* heads_in_layer, const int* slots, int n, hipStream_t stream);
 
 }  // namespace wm

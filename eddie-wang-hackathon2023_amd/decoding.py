@@ -33,7 +33,8 @@ What differs underneath:
 
 This module holds the options, the results and `WhisperDecoding`'s construction and call contract (start rows, prompts, post_process).
 host_decoding.py holds the literal loops and the host filter / decoder classes and imports neither `native` nor `ctypes`;
-device_loop.py holds the device loop, the device language pass and the device word timestamps.  Their public names are re-exported here.
+device_loop.py holds the device loop and the device language pass; word_align.py holds the device word timestamps and the forced pass
+that forced alignment shares.  Their public names are re-exported here.
 """
 from __future__ import annotations
 
@@ -60,6 +61,7 @@ from host_decoding import (BEAM_MAX, BEAM_POOL_MAX, CHUNK_LENGTH, ApplyTimestamp
                            SequenceBias, SuppressBlank, SuppressTokens)
 from session import Session
 from tokenizer import Tokenizer, layout_from_vocab
+from word_align import WordAlign
 
 
 @dataclass(frozen=True)
@@ -184,7 +186,7 @@ def right_aligned_rows(prompts: Sequence[Sequence[int]], sot_sequence: Sequence[
     return rows, starts
 
 
-class WhisperDecoding(HostLoops, DeviceLoop):
+class WhisperDecoding(HostLoops, DeviceLoop, WordAlign):
     def __init__(self, engine_dir, only_torch: bool = False, vocab_path: Optional[str] = None,
                  options: Optional[DecodingOptions] = None, row_prompts: bool = False, shared_cross_kv: bool = False,
                  fallback_best_of: Optional[int] = None, block_prefill: bool = False):

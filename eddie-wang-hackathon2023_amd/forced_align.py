@@ -43,15 +43,14 @@ import native
 import timing
 from alignment import AlignOptions
 from mel_batch import MelBatch, mel_windows
-from tokenizer import Tokenizer
+from word_align import named_language, pass_bytes_per_row, require_fp16_cross_kv
 
 
 def check_align_supported(decoding, n_files: int, texts, options: AlignOptions) -> None:
     """The refusals of the module docstring that need no audio."""
     if not isinstance(options, AlignOptions):
         raise ValueError("align: options must be an alignment.AlignOptions")
-    if getattr(decoding, 'use_int8_cross_kv', False):
-        raise native.WmError("word timestamps need fp16 cross-attention K/V; this engine stores int8 codes (WM_FLAG_INT8_CROSS_KV)")
+    require_fp16_cross_kv(decoding)
     if getattr(decoding, 'cu_partition', False):
         raise ValueError("align: the CU-partitioned schedule (cu_partition = True) is not supported: the forced pass is one block on one stream")
     if decoding.beam or decoding.n_group != 1:
@@ -66,21 +65,9 @@ def check_align_supported(decoding, n_files: int, texts, options: AlignOptions) 
             raise ValueError("align: a text is a string or a list of strings (lines)")
 
 
-def _language(decoding, language: Optional[str]) -> Optional[str]:
-    """The language the call names (argument, else the instance's options), as a code; None: detect per file."""
-    if not decoding.is_multilingual:
-        return 'en'
-    named = language if language is not None else decoding.options.language
-    if named is None:
-        return None
-    return Tokenizer._defaults(True, named, None, decoding.tokenizer.num_languages)[0]
-
-
 def align_pass_bytes_per_row(decoding, options: AlignOptions) -> int:
     """What a row holds beside the decoder state: the tape (heads x L x 128 B) and its paths."""
-    cfg = decoding.decoder_config
-    L = len(decoding.tokenizer.sot_sequence) + 2 + int(options.max_tokens)
-    return len(decoding.alignment_heads()) * L * 128 + 2 * (L + cfg['num_audio_ctx']) * 4 + L * 4
+    return pass_bytes_per_row(decoding, len(decoding.tokenizer.sot_sequence) + 2 + int(options.max_tokens), paths=True)
 
 
 def default_align_rows(decoding, n_files: int, device, options: AlignOptions) -> int:
@@ -129,7 +116,7 @@ def align_mel(encoding, decoding, mels: Sequence[torch.Tensor], content_frames: 
     if len(content_frames) != n_files:
         raise ValueError(f"align: {len(content_frames)} content_frames for {n_files} mels")
     check_align_supported(decoding, n_files, texts, options)
-    named = _language(decoding, language)
+    named = named_language(decoding, language)
     for f, c in enumerate(content_frames):
         if int(c) <= 0:
             raise ValueError(f"align: file {f} has no audio")
@@ -201,18 +188,8 @@ def align_mel(encoding, decoding, mels: Sequence[torch.Tensor], content_frames: 
         tape, probs, cross = decoding._forced_pass_block(features, forced, L, heads_arr, "device", buffers)
         n_tokens.copy_(torch.tensor(n_all, dtype=torch.int32))
         n_frames.copy_(torch.tensor(frames, dtype=torch.int32))
-        io = native.WmAlignIO()
-        io.engine = decoding.decoder_session.engine.handle
-        io.batch, io.n_text_head, io.n_audio_ctx = n_rows, cfg['num_heads'], ctx
-        io.q_tape, io.capacity = tape.data_ptr(), L
-        cross_arr = native.ptr_array(cross)
-        io.cross, io.n_layers = C.cast(cross_arr, C.POINTER(C.c_void_p)), cfg['num_layers']
-        io.heads, io.n_heads = C.cast(heads_arr, C.POINTER(C.c_int32)), len(heads_arr)
-        io.n_tokens, io.n_frames = n_tokens.data_ptr(), n_frames.data_ptr()
-        io.n_prefix, io.filter_width, io.cap_tokens = n_sot, timing.MEDIAN_FILTER_WIDTH, L
-        io.matrix, io.ld = (matrix.data_ptr(), ctx) if matrix is not None else (None, 0)
-        io.path_text, io.path_time, io.path_len = back.data_ptr(), back[o_time:].data_ptr(), back[o_len:].data_ptr()
-        io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
+        io = native.align_io(decoding.decoder_session.engine.handle, cfg['num_heads'], ctx, tape, cross, heads_arr, n_tokens, n_frames,
+                             n_sot, timing.MEDIAN_FILTER_WIDTH, L, matrix, ctx, back, back[o_time:], back[o_len:], ws)
         native.check(lib.wm_align_open(C.byref(io), back[o_end:].data_ptr(), torch.cuda.current_stream().cuda_stream), "wm_align_open")
         host = back.cpu().numpy()                       # the round's one copy back (synchronises)
         pt, pf = host[:o_time].reshape(n_rows, path_ld), host[o_time:o_len].reshape(n_rows, path_ld)
@@ -266,7 +243,7 @@ def align(encoding, decoding, audio_or_paths, texts, language: Optional[str] = N
     import whisper_utils as wu
     audio_or_paths = list(audio_or_paths)
     check_align_supported(decoding, len(audio_or_paths), texts, options)      # before anything is loaded
-    _language(decoding, language)
+    named_language(decoding, language)
     mels, content = [], []
     for f, a in enumerate(audio_or_paths):
         if isinstance(a, (str, Path)):

@@ -503,11 +503,38 @@ def check(rc: int, what: str = ""):
         raise WmError(f"{what or 'libwhisper_mi355'} failed (rc={rc}): {msg}")
 
 
+def _ptr(t):
+    return None if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+
+
+def align_io(engine, n_text_head: int, n_audio_ctx: int, tape, cross: Sequence, heads, n_tokens, n_frames, n_prefix: int,
+             filter_width: int, cap_tokens: int, matrix, ld: int, path_text, path_time, path_len, workspace) -> WmAlignIO:
+    """The wm_align_io of one wm_align / wm_align_open call.  `engine`: the decoder's handle, or None (the dims are then taken on trust);
+    tape fp16 [batch, len(heads), capacity, 64]; cross: per layer fp16 [batch, 2, n_text_head, n_audio_ctx, 64]; heads: a ctypes int32
+    array or a list; matrix: fp32 rows of `ld` elements, or None.  The struct keeps its pointer arrays alive (`io._keep`)."""
+    if not isinstance(heads, C.Array):
+        heads = (C.c_int32 * len(heads))(*heads)
+    cross_arr = ptr_array(cross)
+    io = WmAlignIO()
+    io.engine = engine
+    io.batch, io.n_text_head, io.n_audio_ctx = tape.shape[0], n_text_head, n_audio_ctx
+    io.q_tape, io.capacity = tape.data_ptr(), tape.shape[2]
+    io.cross, io.n_layers = C.cast(cross_arr, C.POINTER(C.c_void_p)), len(cross)
+    io.heads, io.n_heads = C.cast(heads, C.POINTER(C.c_int32)), len(heads)
+    io.n_tokens, io.n_frames = _ptr(n_tokens), _ptr(n_frames)
+    io.n_prefix, io.filter_width, io.cap_tokens = n_prefix, filter_width, cap_tokens
+    io.matrix, io.ld = (_ptr(matrix), ld) if matrix is not None else (None, 0)
+    io.path_text, io.path_time, io.path_len = _ptr(path_text), _ptr(path_time), _ptr(path_len)
+    io.workspace, io.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    io._keep = (cross_arr, heads)
+    return io
+
+
 def ptr_array(tensors: Sequence) -> "C.Array":
     """Device pointers of a list of torch tensors (or ints / None) as a void*[]."""
     arr = (C.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):
-        arr[i] = None if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        arr[i] = _ptr(t)
     return arr
 
 

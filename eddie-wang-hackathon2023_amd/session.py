@@ -293,15 +293,28 @@ class Session(object):
         io = self.make_decoder_io(*lead, **kw)
         check(self._engine.lib.wm_decoder_step(self._engine.handle, C.byref(io), stream), "wm_decoder_step")
 
+    def _prefill_io(self, tokens, pos, cross, present, capacity, logits, logits_from: int, **kw) -> native.WmPrefillIO:
+        """The wm_prefill_io of one block call: the decoder io on the empty cache `present`, and where the logits begin."""
+        pio = native.WmPrefillIO()
+        pio.io = self.make_decoder_io(tokens, pos, cross, None, 0, present, capacity, logits, 0, prefill=True, **kw)
+        pio.logits_from = int(logits_from)
+        pio._keep = pio.io
+        return pio
+
+    @staticmethod
+    def _tap_io(tokens, q_tape: torch.Tensor, heads) -> native.WmTapIO:
+        """The wm_tap_io of one tapped call: q_tape fp16 [B, len(heads), capacity, 64], `heads` a ctypes int32 array the caller keeps."""
+        assert q_tape.dtype == torch.float16 and q_tape.is_contiguous() and q_tape.shape[0] == tokens.shape[0] and q_tape.shape[1] == len(heads)
+        tap = native.WmTapIO()
+        tap.q_tape, tap.capacity = q_tape.data_ptr(), q_tape.shape[2]
+        tap.heads, tap.n_heads = C.cast(heads, C.POINTER(C.c_int32)), len(heads)
+        return tap
+
     def decoder_prefill(self, tokens, pos, cross, present, capacity, logits, stream: int, logits_from: int, slot: int = 0,
                         live_rows=None, row_start=None):
         """wm_decoder_prefill: the whole block tokens int32 [B, L] (L = 1 .. n_text_ctx) on the EMPTY cache `present` (appended in place,
         slots 0 .. L - 1) in one pass; logits fp16 [B, L, V] are written for the positions logits_from .. L - 1 only."""
-        pio = native.WmPrefillIO()
-        pio.io = self.make_decoder_io(tokens, pos, cross, None, 0, present, capacity, logits, 0, slot=slot, live_rows=live_rows,
-                                      row_start=row_start, prefill=True)
-        pio.logits_from = int(logits_from)
-        pio._keep = pio.io
+        pio = self._prefill_io(tokens, pos, cross, present, capacity, logits, logits_from, slot=slot, live_rows=live_rows, row_start=row_start)
         check(self._engine.lib.wm_decoder_prefill(self._engine.handle, C.byref(pio), stream), "wm_decoder_prefill")
 
     def decoder_step_tap(self, tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past, stream: int,
@@ -310,24 +323,15 @@ class Session(object):
         int32 array of layer * n_head + head, ascending) written to rows n_past .. of q_tape fp16 [B, len(heads), capacity, 64]."""
         io = self.make_decoder_io(tokens, pos, cross, past, past_capacity, present, present_capacity, logits, n_past,
                                   slot=slot, not_alone=True)
-        assert q_tape.dtype == torch.float16 and q_tape.is_contiguous() and q_tape.shape[0] == tokens.shape[0] and q_tape.shape[1] == len(heads)
-        tap = native.WmTapIO()
-        tap.q_tape, tap.capacity = q_tape.data_ptr(), q_tape.shape[2]
-        tap.heads, tap.n_heads = C.cast(heads, C.POINTER(C.c_int32)), len(heads)
+        tap = self._tap_io(tokens, q_tape, heads)
         check(self._engine.lib.wm_decoder_step_tap(self._engine.handle, C.byref(io), C.byref(tap), stream), "wm_decoder_step_tap")
 
     def decoder_prefill_tap(self, tokens, pos, cross, present, capacity, logits, stream: int, logits_from: int, q_tape: torch.Tensor,
                             heads, slot: int = 0):
         """wm_decoder_prefill_tap: `decoder_prefill` with the cross-attention queries of `heads` (as decoder_step_tap) written to rows
         0 .. L - 1 of q_tape fp16 [B, len(heads), capacity, 64]."""
-        pio = native.WmPrefillIO()
-        pio.io = self.make_decoder_io(tokens, pos, cross, None, 0, present, capacity, logits, 0, slot=slot, prefill=True)
-        pio.logits_from = int(logits_from)
-        pio._keep = pio.io
-        assert q_tape.dtype == torch.float16 and q_tape.is_contiguous() and q_tape.shape[0] == tokens.shape[0] and q_tape.shape[1] == len(heads)
-        tap = native.WmTapIO()
-        tap.q_tape, tap.capacity = q_tape.data_ptr(), q_tape.shape[2]
-        tap.heads, tap.n_heads = C.cast(heads, C.POINTER(C.c_int32)), len(heads)
+        pio = self._prefill_io(tokens, pos, cross, present, capacity, logits, logits_from, slot=slot)
+        tap = self._tap_io(tokens, q_tape, heads)
         check(self._engine.lib.wm_decoder_prefill_tap(self._engine.handle, C.byref(pio), C.byref(tap), stream), "wm_decoder_prefill_tap")
 
     def decoder_step_multi(self, ios: Sequence[WmDecoderIO], light_streams: Sequence[int], heavy_stream: int):

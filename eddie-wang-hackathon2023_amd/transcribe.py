@@ -89,7 +89,6 @@ import torch
 import channels as channels_mod
 import logit_controls
 import longform
-import native
 import sections as sections_mod
 import speech as speech_mod
 from channels import ChannelOptions
@@ -98,7 +97,7 @@ from encoding import WhisperEncoding
 from mel_batch import MelBatch, channel_top, mel_windows, packed_mels, section_cuts, section_mels, speech_spans  # noqa: F401 (re-exported)
 from sections import SectionOptions
 from speech import SpeechOptions
-from tokenizer import Tokenizer
+from word_align import named_language, pass_bytes_per_row, require_fp16_cross_kv
 
 
 def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], condition_on_previous_text: bool = False,
@@ -109,8 +108,7 @@ def check_supported(decoding: WhisperDecoding, temperatures: Sequence[float], co
         if (decoding.beam or decoding.n_group != 1) and not getattr(decoding, 'shared_cross_kv', False):
             raise ValueError("transcribe: word_timestamps with beam_size / best_of is not supported in this version (the device "
                              "alignment reads one row of cross K/V per file) unless the instance was built with shared_cross_kv=True")
-        if getattr(decoding, 'use_int8_cross_kv', False):
-            raise native.WmError("word timestamps need fp16 cross-attention K/V; this engine stores int8 codes (WM_FLAG_INT8_CROSS_KV)")
+        require_fp16_cross_kv(decoding)
     if opt.prompt or opt.prefix:
         raise ValueError("transcribe: an instance built with options.prompt / options.prefix is not supported: hand the prompt to "
                          "transcribe(initial_prompt=...) with an instance built with row_prompts=True")
@@ -129,7 +127,7 @@ def word_pass_bytes_per_row(decoding: WhisperDecoding) -> int:
     at most n_text_ctx) and the fp16 logits of a 4-token call."""
     cfg = decoding.decoder_config
     l_max = min(cfg['num_text_ctx'], len(decoding.tokenizer.sot_sequence) + 2 + int(decoding.sample_len))
-    return len(decoding.alignment_heads()) * l_max * 128 + 4 * cfg['vocab_size'] * 2
+    return pass_bytes_per_row(decoding, l_max) + 4 * cfg['vocab_size'] * 2
 
 
 def default_rows(decoding: WhisperDecoding, n_files: int, device, word_timestamps: bool = False) -> int:
@@ -224,7 +222,7 @@ def _split_sections(batch: MelBatch, W: int, fs: float, options: SectionOptions,
             mine = [i for i, o in enumerate(owner) if o == f]
             segments = sections_mod.merge_sections([parts[i]['segments'] for i in mine], [starts[i] for i in mine], fs)
             text = decoding.tokenizer.decode([t for s in segments for t in s['tokens']]).strip()
-            language = parts[mine[0]]['language'] if mine else _language_without_audio(decoding)
+            language = parts[mine[0]]['language'] if mine else named_language(decoding)
             out.append(dict(language=language, text=text, segments=segments,
                             sections=[(starts[i] * fs, (starts[i] + piece_frames[i]) * fs) for i in mine]))
         return out
@@ -316,17 +314,6 @@ def transcribe_mel(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: S
     return _transcribe_layers(encoding, decoding, batch, W, fs, kw, None, speech, sections)
 
 
-def _named_language(decoding: WhisperDecoding) -> Optional[str]:
-    if decoding.is_multilingual and decoding.options.language is not None:
-        return Tokenizer._defaults(True, decoding.options.language, None, decoding.tokenizer.num_languages)[0]
-    return None
-
-
-def _language_without_audio(decoding: WhisperDecoding) -> Optional[str]:
-    """What a file says of its language before any window of it was heard: the named one, None until detected."""
-    return _named_language(decoding) if decoding.is_multilingual else 'en'
-
-
 def _transcribe_files(encoding: WhisperEncoding, decoding: WhisperDecoding, mels: Sequence[torch.Tensor],
                       content_frames: Sequence[int], owner: Optional[Sequence[int]], *, temperatures, compression_ratio_threshold,
                       logprob_threshold, no_speech_threshold, n_rows, trace, condition_on_previous_text, initial_prompt,
@@ -360,8 +347,8 @@ def _transcribe_files(encoding: WhisperEncoding, decoding: WhisperDecoding, mels
 
     # the language of every file: named by the options, or detected on the file's first window (of its first section)
     multilingual = decoding.is_multilingual
-    named = _named_language(decoding)
-    languages = sections_mod.SectionLanguages(n_files, owner, _language_without_audio(decoding))
+    named = named_language(decoding)                    # (what a file says before any window of it was heard: None until detected)
+    languages = sections_mod.SectionLanguages(n_files, owner, named)
     default_token = tk.special_tokens[f"<|{named or 'en'}|>"] if multilingual else None
 
     win = torch.zeros((n_rows, n_mels, W), dtype=torch.float16, device=dev)

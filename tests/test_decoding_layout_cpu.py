@@ -1,5 +1,5 @@
-"""Where the decoding code lives (no GPU, no engine): decoding.py assembles `WhisperDecoding` from the literal loops of host_decoding.py
-and the device loop of device_loop.py and re-exports their public names.  The lists below are written out: the names imported from
+"""Where the decoding code lives (no GPU, no engine): decoding.py assembles `WhisperDecoding` from the literal loops of host_decoding.py,
+the device loop of device_loop.py and the word alignment of word_align.py and re-exports their public names.  The lists below are written out: the names imported from
 `decoding` anywhere in the repository before the split, and what `dir(WhisperDecoding)` held then."""
 import ast
 import os
@@ -8,6 +8,7 @@ import types
 import decoding
 import device_loop
 import host_decoding
+import word_align
 from decoding import WhisperDecoding
 
 # every name that tests/, scripts/, bench.py, oracle/, __graft_entry__.py or the package imports from `decoding`
@@ -32,6 +33,9 @@ CLASS_ATTRIBUTES = [
     "get_tokenizer", "main_loop", "main_loop_reference", "post_process", "set_language_tokens", "set_prompts",
     "state_bytes_per_utterance", "torch_detect_language", "torch_main_loop", "torch_word_timestamps", "word_timestamps",
     "xa2cross_key_value"]
+
+WORD_ALIGN_MIXIN = ["word_timestamps", "block_pass_rows", "BLOCK_LOGIT_BYTES", "_forced_pass", "_forced_pass_block", "_align",
+                    "_words_from_paths"]
 
 HOST_MIXIN = ["xa2cross_key_value", "_features_key", "decode", "_language_from_logits", "detect_language_reference", "torch_detect_language",
               "_host_call", "_host_step", "main_loop_reference", "torch_main_loop", "torch_word_timestamps"]
@@ -64,8 +68,34 @@ def test_the_class_keeps_its_names():
     assert not missing, missing
     assert decoding.WhisperDecoding.__module__ == "decoding"
     assert all(n in vars(host_decoding.HostLoops) for n in HOST_MIXIN)
-    assert all(n in vars(device_loop.DeviceLoop) for n in ("_fast_state", "_finish_beam_loop", "detect_language", "word_timestamps",
+    assert all(n in vars(device_loop.DeviceLoop) for n in ("_fast_state", "_finish_beam_loop", "detect_language",
                                                            "_main_loop_partitioned", "_check_partition", "_chain_gave_up"))
+    assert all(n in vars(word_align.WordAlign) for n in WORD_ALIGN_MIXIN)
+    assert not any(n in vars(device_loop.DeviceLoop) or hasattr(device_loop, n) for n in WORD_ALIGN_MIXIN)
+    assert WhisperDecoding.__mro__[1:4] == (host_decoding.HostLoops, device_loop.DeviceLoop, word_align.WordAlign)
+
+
+def test_word_align_stands_beside_the_loops():
+    assert not {"decoding", "device_loop"} & _imported_modules(word_align)
+    assert "decoding" not in vars(word_align) and "device_loop" not in vars(word_align)
+    assert os.path.dirname(word_align.__file__) == os.path.dirname(decoding.__file__)
+
+
+def test_one_construction_of_the_align_io():
+    """native.align_io fills the wm_align_io for every caller: forced alignment and the two GPU test files have no construction of
+    their own, and the package has one."""
+    here, pkg = os.path.dirname(os.path.abspath(__file__)), os.path.dirname(decoding.__file__)
+    paths = [os.path.join(here, "test_gpu_word_timestamps.py"), os.path.join(here, "test_gpu_dtw_open.py")]
+    paths += [os.path.join(pkg, f) for f in sorted(os.listdir(pkg)) if f.endswith(".py")]
+    found = []
+    for path in paths:
+        with open(path) as f:
+            tree = ast.parse(f.read())
+        for node in ast.walk(tree):
+            callee = node.func if isinstance(node, ast.Call) else None
+            if getattr(callee, "attr", None) == "WmAlignIO" or getattr(callee, "id", None) == "WmAlignIO":
+                found.append(os.path.basename(path))
+    assert found == ["native.py"], found
 
 
 def test_the_literal_loops_need_no_library():

@@ -108,7 +108,6 @@ def test_align_open_matrix_is_wm_aligns_and_its_walk_is_dtw_open_cpu():
     cross = [torch.randn(Bn, 2, H, Tk, 64, generator=g).half().cuda() for _ in range(n_layers)]
     nt, nf = torch.tensor(n_tokens, dtype=torch.int32).cuda(), torch.tensor(n_frames, dtype=torch.int32).cuda()
     ld, path_ld = Tk + 4, cap + Tk
-    heads_arr, cross_arr = (C.c_int32 * len(heads))(*heads), native.ptr_array(cross)
     out = {}
     for name in ("closed", "open"):
         matrix = torch.full((Bn, cap, ld), 777.0, dtype=torch.float32).cuda()
@@ -116,17 +115,7 @@ def test_align_open_matrix_is_wm_aligns_and_its_walk_is_dtw_open_cpu():
         pf = torch.full((Bn, path_ld), -7, dtype=torch.int32).cuda()
         pl, er = torch.full((Bn,), -7, dtype=torch.int32).cuda(), torch.full((Bn,), -7, dtype=torch.int32).cuda()
         ws = torch.empty(lib.wm_align_workspace_bytes(Bn, len(heads), cap, Tk), dtype=torch.uint8).cuda()
-        io = native.WmAlignIO()
-        io.engine = None
-        io.batch, io.n_text_head, io.n_audio_ctx = Bn, H, Tk
-        io.q_tape, io.capacity = tape.data_ptr(), cap
-        io.cross, io.n_layers = C.cast(cross_arr, C.POINTER(C.c_void_p)), n_layers
-        io.heads, io.n_heads = C.cast(heads_arr, C.POINTER(C.c_int32)), len(heads)
-        io.n_tokens, io.n_frames = nt.data_ptr(), nf.data_ptr()
-        io.n_prefix, io.filter_width, io.cap_tokens = n_prefix, 7, cap
-        io.matrix, io.ld = matrix.data_ptr(), ld
-        io.path_text, io.path_time, io.path_len = pt.data_ptr(), pf.data_ptr(), pl.data_ptr()
-        io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
+        io = native.align_io(None, H, Tk, tape, cross, heads, nt, nf, n_prefix, 7, cap, matrix, ld, pt, pf, pl, ws)
         stream = torch.cuda.current_stream().cuda_stream
         rc = lib.wm_align(C.byref(io), stream) if name == "closed" else lib.wm_align_open(C.byref(io), er.data_ptr(), stream)
         torch.cuda.synchronize()

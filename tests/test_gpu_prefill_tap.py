@@ -1,4 +1,4 @@
-"""wm_decoder_prefill_tap on a real MI355X (csrc/decoder.hip, tap_q_block_kernel in csrc/align.hip): the block
+"""wm_decoder_prefill_tap on a real MI355X (csrc/decoder.hip, tap_q_kernel in csrc/align.hip): the block
 prefill with the cross-attention queries of the alignment heads taped.  Logits and cache are wm_decoder_prefill's bit for bit, tape
 rows beyond n_new keep their sentinel, and the tape is the oracle's cross-attention query (fed the block whole, as the block-prefill
 tests feed it) within the project's teacher-forced bounds: LOGIT_TOL, and LOGIT_TOL_INT8_KV for an int8 self-K/V engine.

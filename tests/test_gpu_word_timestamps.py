@@ -130,19 +130,7 @@ def run_align(tape, cross, heads, H, Tk, n_tokens, n_frames, n_prefix, cap, want
     nt = torch.tensor(n_tokens, dtype=torch.int32).cuda()
     nf = torch.tensor(n_frames, dtype=torch.int32).cuda()
     ws = torch.empty(lib.wm_align_workspace_bytes(Bn, nh, cap, Tk), dtype=torch.uint8).cuda()
-    heads_arr = (C.c_int32 * nh)(*heads)
-    cross_arr = native.ptr_array(cross)
-    io = native.WmAlignIO()
-    io.engine = engine
-    io.batch, io.n_text_head, io.n_audio_ctx = Bn, H, Tk
-    io.q_tape, io.capacity = tape.data_ptr(), tape.shape[2]
-    io.cross, io.n_layers = C.cast(cross_arr, C.POINTER(C.c_void_p)), len(cross)
-    io.heads, io.n_heads = C.cast(heads_arr, C.POINTER(C.c_int32)), nh
-    io.n_tokens, io.n_frames = nt.data_ptr(), nf.data_ptr()
-    io.n_prefix, io.filter_width, io.cap_tokens = n_prefix, 7, cap
-    io.matrix, io.ld = (matrix.data_ptr(), ld) if want_matrix else (None, 0)
-    io.path_text, io.path_time, io.path_len = pt.data_ptr(), pf.data_ptr(), pl.data_ptr()
-    io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
+    io = native.align_io(engine, H, Tk, tape, cross, heads, nt, nf, n_prefix, 7, cap, matrix if want_matrix else None, ld, pt, pf, pl, ws)
     rc = lib.wm_align(C.byref(io), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return rc, matrix.cpu().numpy(), pt.cpu().numpy(), pf.cpu().numpy(), pl.cpu().tolist()
