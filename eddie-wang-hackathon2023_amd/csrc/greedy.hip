@@ -150,8 +150,10 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_kernel(GreedyParams p) 
         // per-row sample_len: the row has sampled its quota -> it ends here, like the reference's loop at sample_len
         // (no log-probability for the closing EOT, W/decoding.py:794,817-821 + finalize :296-300)
         const bool capped = alive && p.row_limit && (cur_len - p.sample_begin >= p.row_limit[b]);
-        if (alive && !capped) p.sum_logprobs[b] += lp;
-        const int next = (alive && !capped) ? best.i : p.eot;
+        // a row with no finite allowed logit ends, as a beam without a live candidate does (beam.hip): EOT at -inf, done, counted
+        const bool empty = best.i == 0x7fffffff;
+        if (alive && !capped) p.sum_logprobs[b] = empty ? -INFINITY : p.sum_logprobs[b] + lp;
+        const int next = (alive && !capped && !empty) ? best.i : p.eot;
         toks[cur_len] = next;
         if (next == p.eot) {
             if (p.n_done) atomicAdd(p.n_done, 1);

@@ -12,7 +12,9 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t x) {
 }
 __device__ __forceinline__ float gumbel_noise(uint32_t key, int n) {
     const uint32_t h = fmix32(fmix32(key ^ ((uint32_t)n * 0x27d4eb2fu)) + 0x9e3779b9u * (uint32_t)n);
-    const float u = ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);          // (0, 1), 24 bits
+    // (0, 1), 24 bits.  Above 2^23 the + 0.5f rounds to even: 16777215 + 0.5 would become 2^24, u = 1 and g = +inf (a token drawn
+    // whatever its logit, once in 2^24 tokens); the bound keeps u <= 1 - 2^-24 and g <= 16.64
+    const float u = fminf((float)(h >> 8) + 0.5f, 16777215.0f) * (1.0f / 16777216.0f);
     return -__logf(-__logf(u));
 }
 

@@ -262,8 +262,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleParams sp)
     const int prev = toks[cur_len - 1];
     const bool alive = (prev != p.eot);
     const bool capped = alive && p.row_limit && (cur_len - p.sample_begin >= p.row_limit[b]);
-    if (alive && !capped) p.sum_logprobs[b] += lp;
-    const int next = (alive && !capped) ? best.i : p.eot;
+    // a row with no finite allowed logit ends, as in greedy_kernel: EOT at -inf, done, counted
+    const bool empty = best.i == 0x7fffffff;
+    if (alive && !capped) p.sum_logprobs[b] = empty ? -INFINITY : p.sum_logprobs[b] + lp;
+    const int next = (alive && !capped && !empty) ? best.i : p.eot;
     toks[cur_len] = next;
     if (next == p.eot) {
         if (p.n_done) atomicAdd(p.n_done, 1);

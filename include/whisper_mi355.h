@@ -267,7 +267,10 @@ int wm_stream_destroy(wm_stream_t stream);
  * Applies SuppressBlank / SuppressTokens / ApplyTimestampRules to the last-position logits of each
  * utterance, picks the arg-max, accumulates its log-probability, keeps finished rows at EOT and
  * appends the token at tokens[b][cur_len].  n_done (device int32, caller zeroes it) counts rows
- * whose new token is EOT.                                                                          */
+ * whose new token is EOT.
+ * A live row with no finite allowed logit (everything the rules leave is -inf) ends, as a beam without a
+ * live candidate does in wm_beam_step: EOT is appended, done[b] is set, the row counts in n_done and
+ * sum_logprobs[b] becomes -inf.  wm_sample_step does the same (its kept_out is then 0, cut_out -inf). */
 typedef struct wm_greedy_io {
     void* logits; int64_t row_stride; /* fp16; row b starts at logits + b*row_stride elements;
                                          suppressed entries are overwritten with -inf in place,
