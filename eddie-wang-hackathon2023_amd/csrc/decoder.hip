@@ -945,6 +945,20 @@ int wm_sample_step(const wm_sample_io* io, wm_stream_t stream) {
     return launch_sample(sp, (hipStream_t)stream);
 }
 
+// ================================================================================================ speculative decoding: verify
+size_t wm_verify_workspace_bytes(int batch, int n_pos) { return verify_workspace_bytes(batch, n_pos); }
+
+int wm_verify_step(const wm_verify_io* io, wm_stream_t stream) {
+    WM_REQUIRE(io && io->g.logits && io->g.tokens && io->g.sum_logprobs && io->n_accept && io->workspace, "wm_verify_step: null argument");
+    WM_REQUIRE(io->g.temperature == 0.f, "wm_verify_step: temperature must be 0 (a sampled token cannot be verified against a proposal)");
+    WM_REQUIRE(!io->g.n_past_dev && !io->g.seed_dev, "wm_verify_step: n_past_dev / seed_dev must be NULL (cur_len is a host value)");
+    VerifyParams vp{};
+    vp.g = greedy_params(&io->g);
+    vp.pos_stride = (long)io->pos_stride; vp.n_pos = io->n_pos;
+    vp.n_accept = io->n_accept; vp.cand = (VerifyCand*)io->workspace;
+    return launch_verify(vp, (hipStream_t)stream);
+}
+
 int wm_step_advance(int32_t* counter, wm_stream_t stream) { return launch_step_advance(counter, (hipStream_t)stream); }
 int wm_step_finish(int32_t* counter, const int32_t* done, int batch, int32_t* live, wm_stream_t stream) {
     return launch_step_finish(counter, done, batch, live, (hipStream_t)stream);

@@ -291,6 +291,17 @@ struct SampleParams {
     float* cut_out; int32_t* kept_out;       // optional [B]: the value of the last kept class, the number of kept tokens
 };
 int launch_sample(const SampleParams& p, hipStream_t stream);
+// ---------------------------------------------------------------- speculative.hip
+struct VerifyCand { int32_t tok; float lp; };    // the main engine's token of one (row, position) and its log-probability (tok = 0x7fffffff: none)
+struct VerifyParams {
+    GreedyParams g;                          // logits = position 0 of row 0; cur_len = first slot to fill (host value); temperature 0, no t_dev
+    long pos_stride;                         // elements between the logits rows of consecutive positions of one utterance
+    int n_pos;                               // 1 .. 4
+    int32_t* n_accept;                       // [B]: slots written
+    VerifyCand* cand;                        // [B][n_pos] scratch between the two launches
+};
+size_t verify_workspace_bytes(int batch, int n_pos);
+int launch_verify(const VerifyParams& p, hipStream_t stream);
 int launch_step_advance(int32_t* counter, hipStream_t stream);
 int launch_step_finish(int32_t* counter, const int32_t* done, int B, int32_t* live, hipStream_t stream);
 // ... and, for candidate groups of G rows (B % G == 0), the utterances with a live row: live_utt[0] = their number, then their indices, ascending

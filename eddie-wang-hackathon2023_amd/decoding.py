@@ -29,7 +29,9 @@ What differs underneath:
 * `top_k` / `top_p` / `min_p` (Hugging Face / CTranslate2; truncation.py states the contract): above temperature 0 the draw is restricted to
   a kept set -- `GreedyDecoder` masks its Categorical in the literal loops, wm_sample_step (csrc/truncate.hip) takes the place of
   wm_greedy_step in the token step of `main_loop`, only for calls at temperature > 0 on an instance with one of them on.  At
-  temperature 0 and under beam search they are inert.
+  temperature 0 and under beam search they are inert;
+* `draft_engine_dir` / `draft_tokens` select speculative decoding (speculative.py states the contract, speculative_loop.py holds the loop):
+  a draft engine proposes, one pass of this engine verifies, wm_verify_step (csrc/speculative.hip) keeps this engine's own tokens.
 
 This module holds the options, the results and `WhisperDecoding`'s construction and call contract (start rows, prompts, post_process).
 host_decoding.py holds the literal loops and the host filter / decoder classes and imports neither `native` nor `ctypes`;
@@ -60,6 +62,7 @@ from host_decoding import (BEAM_MAX, BEAM_POOL_MAX, CHUNK_LENGTH, ApplyTimestamp
                            GreedyDecoder, HostLoops, LogitFilter, MaximumLikelihoodRanker, NoRepeatNGram, RepetitionPenalty,
                            SequenceBias, SuppressBlank, SuppressTokens)
 from session import Session
+from speculative_loop import SpeculativeLoop
 from tokenizer import Tokenizer, layout_from_vocab
 from word_align import WordAlign
 
@@ -186,10 +189,10 @@ def right_aligned_rows(prompts: Sequence[Sequence[int]], sot_sequence: Sequence[
     return rows, starts
 
 
-class WhisperDecoding(HostLoops, DeviceLoop, WordAlign):
+class WhisperDecoding(HostLoops, DeviceLoop, WordAlign, SpeculativeLoop):
     def __init__(self, engine_dir, only_torch: bool = False, vocab_path: Optional[str] = None,
                  options: Optional[DecodingOptions] = None, row_prompts: bool = False, shared_cross_kv: bool = False,
-                 fallback_best_of: Optional[int] = None, block_prefill: bool = False):
+                 fallback_best_of: Optional[int] = None, block_prefill: bool = False, draft_engine_dir=None, draft_tokens: int = 3):
         """`shared_cross_kv` (opt-in): the n_group candidates of an utterance (beams, best_of samples) read ONE copy of its
         cross-attention K/V (wm_decoder_group_io::cross_group) instead of a copy each: the cross K/V are projected once from the
         un-repeated features, held once per utterance and streamed once per utterance and token step.  Device loop only; not
@@ -213,7 +216,16 @@ class WhisperDecoding(HostLoops, DeviceLoop, WordAlign):
         pass of word_timestamps and every decode step are unchanged.  Not with int8 cross K/V engines, not with `cu_partition`.
         It pays at every row count measured (scripts/bench_prompts.py, large-v2 int8, L0 = 227): time to the first
         token 117.6 -> 5.4 ms at one row, 202.9 -> 17.8 ms at 8, 613.3 -> 91.9 ms at 64 with full prompts, and as much without prompts;
-        no row count was found where it is not lower.  A start block of up to 4 tokens never takes it."""
+        no row count was found where it is not lower.  A start block of up to 4 tokens never takes it.
+        `draft_engine_dir` (opt-in): speculative decoding (speculative.py states the contract).  A second decoder
+        over the engines of that directory -- a model with the same encoder output, context and vocabulary and fewer decoder layers:
+        distil-large-v3 or large-v3-turbo beside large-v3 -- proposes `draft_tokens` (1 .. 3) tokens per round under Whisper's rules, ONE
+        wm_decoder_step of this instance's engine over the last token and the proposals verifies them, and wm_verify_step keeps the
+        tokens this engine would have chosen itself: 1 to draft_tokens + 1 per pass over the weights.  `main_loop` at temperature 0
+        then decodes the rows one after another (a latency mode for one long file, not a throughput mode); calls at temperature > 0
+        take the ordinary loop.  The results are this engine's; `speculative_stats` holds the rounds, proposals, accepted proposals
+        and sampled tokens per row of the last call.  Not with beam_size / best_of / fallback_best_of, row_prompts, shared_cross_kv,
+        cu_partition, the repetition controls or hotwords / sequence_bias.  An instance without a draft launches what it always did."""
         engine_dir = Path(engine_dir)
         self.decoder_config = None
         self.cross_attn_config = None
@@ -249,6 +261,7 @@ class WhisperDecoding(HostLoops, DeviceLoop, WordAlign):
             self.positional_embedding = self.positional_embedding.to('cuda').type(torch.float16).contiguous()
         self._init_decoder()
         self._init_schedule()
+        self._init_draft(draft_engine_dir, draft_tokens, bool(row_prompts), fallback_best_of)
         WhisperDecoding._instances.add(self)      # (weak: a give-up of a one-launch step drops the graphs of EVERY instance, _chain_gave_up)
 
     _chain_warned = False                 # the give-up warning of the device loop (_chain_gave_up): once per process, re-armed here
@@ -435,6 +448,8 @@ class WhisperDecoding(HostLoops, DeviceLoop, WordAlign):
         if not language_tokens or any(t not in valid for t in language_tokens):
             raise ValueError("set_language_tokens: need one language token of the vocabulary per row")
         self.tokens = self._start_rows(len(language_tokens), torch.tensor(language_tokens, dtype=torch.long))
+        if self.draft is not None:        # (the draft reads the main token rows; its own start rows follow for its literal loops)
+            self.draft.set_language_tokens(language_tokens)
 
     def set_prompts(self, prompts: Optional[Sequence[Sequence[int]]]) -> None:
         """Hand in the prompt (token ids) of every utterance of the next main_loop calls -- the previous windows' text of a

@@ -676,6 +676,10 @@ class DeviceLoop:
         beam = self.beam and decoder is self.decoder        # this call's decoder (fallback_best_of: samples above temperature 0)
         G = self._cross_group()
         self._check_device_call(audio_features, temp)
+        if getattr(self, 'draft', None) is not None and temp == 0 and not ignore_eot:
+            # speculative decoding (speculative_loop.py): row after row, the draft proposes and one pass of this engine verifies.
+            # Calls above temperature 0 (the long-form ladder) and fixed-length benchmark loops take the ordinary loop below
+            return self._speculative_loop(audio_features, row_limit=row_limit, _retry=_retry)
         if temp != 0 or self.n_group != 1 or self.beam:
             # Sampling options (W/decoding.py:274-300 temperature, :92-115 best_of + ranker).  Round 4: the device loop takes them --
             # the draw is a Gumbel-max inside the greedy kernel, candidates are rows like any others.  `device_sampling = False`

@@ -95,6 +95,7 @@ EXPORTS = (
     "wm_sample_step",
     "wm_resample_channels", "wm_channel_top_workspace_bytes", "wm_channel_top",
     "wm_dtw_open", "wm_align_open", "wm_decoder_prefill_tap",
+    "wm_verify_workspace_bytes", "wm_verify_step",
 )
 
 
@@ -237,6 +238,15 @@ class WmSampleIO(C.Structure):
         ("g", WmGreedyIO),
         ("top_k", C.c_int32), ("exp2_scale", C.c_float), ("top_p_q16", C.c_int32), ("min_p_gap", C.c_float),
         ("cut_out", C.c_void_p), ("kept_out", C.c_void_p),
+    ]
+
+
+class WmVerifyIO(C.Structure):
+    """wm_verify_io (include/whisper_mi355.h): the verify step of speculative decoding over n_pos positions of every row."""
+    _fields_ = [
+        ("g", WmGreedyIO),
+        ("pos_stride", C.c_int64), ("n_pos", C.c_int32),
+        ("n_accept", C.c_void_p), ("workspace", C.c_void_p),
     ]
 
 
@@ -450,6 +460,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.wm_repeat_controls.argtypes = [C.POINTER(WmRepeatIO), vp]
     lib.wm_sequence_bias.argtypes = [C.POINTER(WmBiasIO), vp]
     lib.wm_sample_step.argtypes = [C.POINTER(WmSampleIO), vp]
+    lib.wm_verify_workspace_bytes.argtypes = [i32, i32]
+    lib.wm_verify_workspace_bytes.restype = sz
+    lib.wm_verify_step.argtypes = [C.POINTER(WmVerifyIO), vp]
     lib.wm_step_advance.argtypes = [vp, vp]
     lib.wm_step_finish.argtypes = [vp, vp, i32, vp, vp]
     lib.wm_beam_workspace_bytes.argtypes = [i32, i32]

@@ -40,6 +40,10 @@ def parse_arguments(argv=None):
                         help="beam search: the beams of an utterance read one copy of its cross-attention K/V (off by default); lets --word_timestamps run with --beam_size")
     parser.add_argument('--word_timestamps', default=False, action='store_true',
                         help='print "start-end word (probability)" lines after the text (cross-attention alignment + DTW on the device; with --beam_size it needs --shared_cross_kv)')
+    parser.add_argument('--draft_engine_dir', type=str, default=None,
+                        help='speculative decoding: the engines of a draft model with the same encoder output, context and vocabulary '
+                             '(distil-large-v3 / large-v3-turbo beside large-v3); greedy only')
+    parser.add_argument('--draft_tokens', type=int, default=3, help='speculative decoding: proposals per round (1..3)')
     logit_controls.add_arguments(parser)
     return parser.parse_args(argv)
 
@@ -74,14 +78,16 @@ def generate(log_level: str = 'error', engine_dir: str = 'whisper_outputs', inpu
              vocab: str = None, beam_size: int = None, patience: float = None, word_timestamps: bool = False,
              shared_cross_kv: bool = False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              hotwords: str = None, hotword_bias: float = biasing.HOTWORD_BIAS, hotword_start_bias: float = biasing.HOTWORD_START_BIAS,
-             sequence_bias_file: str = None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+             sequence_bias_file: str = None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
+             draft_engine_dir: str = None, draft_tokens: int = 3):
     options = decoding_options(argparse.Namespace(**locals()))                  # (the keywords are parse_arguments' names)
     logging.basicConfig(level=getattr(logging, log_level.upper(), logging.ERROR))
     torch.cuda.set_device(0)
     engine_dir = Path(engine_dir)
     whisper_encoding = WhisperEncoding(engine_dir)
     mel = load_mel(input_file, whisper_encoding.num_mels).to('cuda').type(torch.float16).unsqueeze(0)
-    whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=options, shared_cross_kv=shared_cross_kv)
+    whisper_decoding = WhisperDecoding(engine_dir, vocab_path=vocab, options=options, shared_cross_kv=shared_cross_kv,
+                                       draft_engine_dir=Path(draft_engine_dir) if draft_engine_dir else None, draft_tokens=draft_tokens)
     begin_time = time.time()
     audio_features = whisper_encoding.get_audio_features(mel)
     languages, language_probs = whisper_decoding.detect_language(audio_features)

@@ -537,6 +537,11 @@ def parse_arguments(argv=None):
                         help="with --channels split: silence a channel's frames where another channel is louder by this many dB "
                              '(microphones that hear each other; off by default -- on a telephone line it would mute the quieter party '
                              'of an overlap; an untuned parameter)')
+    parser.add_argument('--draft_engine_dir', type=str, default=None,
+                        help='speculative decoding at temperature 0 (WhisperDecoding(draft_engine_dir=...)): the engines of a draft model with '
+                             'the same encoder output, context and vocabulary; rows are decoded one after another, so it serves one long '
+                             'file without --sections; not with --beam_size / --best_of, prompts, the repetition controls or a bias')
+    parser.add_argument('--draft_tokens', type=int, default=3, help='speculative decoding: proposals per round (1..3)')
     logit_controls.add_arguments(parser)
     return parser.parse_args(argv)
 
@@ -558,18 +563,20 @@ def build_decoding(args, engine_dir, prompted: bool) -> WhisperDecoding:
     --no_repeat_ngram_size, --hotwords / --sequence_bias_file and --top_k / --top_p / --min_p go into the instance's options: every window, temperature and section
     decodes through it."""
     repeat = logit_controls.options_from_args(args)
+    draft = getattr(args, 'draft_engine_dir', None)
+    draft = dict(draft_engine_dir=Path(draft), draft_tokens=getattr(args, 'draft_tokens', 3)) if draft else {}    # (refusals: WhisperDecoding's)
     if args.beam_size is not None:
         options = DecodingOptions(language=args.language, beam_size=args.beam_size, patience=args.patience, **repeat)
         return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,
-                               fallback_best_of=args.best_of if args.best_of is not None else 1, block_prefill=args.block_prefill)
+                               fallback_best_of=args.best_of if args.best_of is not None else 1, block_prefill=args.block_prefill, **draft)
     if args.patience is not None:
         raise ValueError("--patience needs --beam_size")
     if args.best_of is not None:
         options = DecodingOptions(language=args.language, best_of=args.best_of, temperature=float(args.temperature[0]), **repeat)
         return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=options, row_prompts=prompted, shared_cross_kv=True,
-                               block_prefill=args.block_prefill)
+                               block_prefill=args.block_prefill, **draft)
     return WhisperDecoding(engine_dir, vocab_path=args.vocab, options=DecodingOptions(language=args.language, **repeat), row_prompts=prompted,
-                           block_prefill=args.block_prefill)
+                           block_prefill=args.block_prefill, **draft)
 
 
 def main(args) -> List[dict]:

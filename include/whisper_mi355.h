@@ -75,7 +75,8 @@ typedef struct wm_dims {
  *      (still 8: an entry and structs of its own) wm_sequence_bias / wm_bias_io / wm_bias_item
  *      (still 8: an entry and a struct of its own) wm_sample_step / wm_sample_io
  *      (still 8: entries only) wm_resample_channels, wm_channel_top, wm_channel_top_workspace_bytes
- *      (still 8: entries only) wm_dtw_open, wm_align_open, wm_decoder_prefill_tap */
+ *      (still 8: entries only) wm_dtw_open, wm_align_open, wm_decoder_prefill_tap
+ *      (still 8: entries and a struct of its own) wm_verify_step / wm_verify_io, wm_verify_workspace_bytes */
 #define WM_ABI_VERSION 8
 int wm_version(void);
 const char* wm_last_error(void);
@@ -412,6 +413,36 @@ typedef struct wm_sample_io {
     int32_t* kept_out;                        /* optional int32 [batch] */
 } wm_sample_io;
 int wm_sample_step(const wm_sample_io* io, wm_stream_t stream);
+
+/* ---- speculative decoding: the verify step (added within ABI 8: entries and a struct of its own) ----------------------
+ * A draft engine has proposed tokens for slots cur_len .. cur_len + n_pos - 2 of every row; ONE wm_decoder_step of the main engine
+ * with n_new = n_pos has written logits for the positions cur_len - 1 .. cur_len + n_pos - 2 (logits row j of a row decides slot
+ * cur_len + j).  This step takes the place of n_pos wm_greedy_step calls (speculative.py states the contract on the host; DESIGN.md
+ * section 5p).  Per row and j = 0, 1, ...: m_j = the token wm_greedy_step would pick at cur_len + j from logits row j given the history
+ * as it then stands (rules included: apply_rules 0 / 1 / 2, the first sampled position, every state of the timestamp rules).  m_j is
+ * written to slot cur_len + j and its log-probability added to the row's sum; the walk stops when m_j is EOT (done / n_done are set as
+ * wm_greedy_step sets them), when j == n_pos - 1, or when m_j differs from the proposal that stood in that slot.  n_accept[b] = the
+ * slots written, 1 .. n_pos.  A row whose previous token (slot cur_len - 1) is EOT writes nothing and reports 0 -- unlike
+ * wm_greedy_step, which keeps appending EOT.  row_limit and the row with no finite allowed logit behave as in wm_greedy_step.
+ * BIT FOR BIT: tokens, sum_logprobs, done and n_done after the call are what n_accept[b] successive wm_greedy_step calls at temperature
+ * 0 leave behind (the two kernels share one definition of the scan, csrc/greedy_scan.h).  Slots behind the last one written keep the
+ * proposals.  The suppress lists are written as -inf into all n_pos logits rows of a live row, whatever n_accept turns out to be.
+ * Two launches: one workgroup per (row, position), then one small launch that walks every row's candidates; `workspace` carries the
+ * candidates between them (wm_verify_workspace_bytes(batch, n_pos) bytes, 8-byte aligned, no initialisation).
+ * Refused (rc 1, nothing launched): a null io / logits / tokens / sum_logprobs / n_accept / workspace; g.temperature != 0;
+ * g.n_past_dev or g.seed_dev set; n_pos outside [1, 4]; batch outside [1, 65535]; n_vocab < 1; cur_len < 1 or
+ * cur_len + n_pos > tokens_ld; pos_stride < n_vocab with n_pos > 1; g.row_stride < (n_pos - 1) * pos_stride + n_vocab with batch > 1 (the
+ * positions of one row would run into the next row); a workspace that is not 8-byte aligned.  Asynchronous on `stream`, no allocation, capturable. */
+typedef struct wm_verify_io {
+    wm_greedy_io g;       /* g.logits = position 0 of row 0; g.cur_len = first slot to fill (host value);
+                             g.temperature must be 0, g.n_past_dev and g.seed_dev NULL */
+    int64_t pos_stride;   /* elements between the logits rows of consecutive positions of one utterance */
+    int32_t n_pos;        /* 1 .. 4 */
+    int32_t* n_accept;    /* device int32 [batch] */
+    void* workspace;      /* wm_verify_workspace_bytes(batch, n_pos) */
+} wm_verify_io;
+size_t wm_verify_workspace_bytes(int batch, int n_pos);
+int wm_verify_step(const wm_verify_io* io, wm_stream_t stream);
 
 /* ---- beam search step (added within ABI 8: new entries only, no existing struct or signature changed) ----------------
  * The semantics of upstream Whisper's BeamSearchDecoder.update on the device, one call per token step of an utterance
